@@ -16,12 +16,24 @@ one, `python bench.py --gpus N` starts its N ranks itself, as a child process, b
 The JSON line: `value` is measured over EXACTLY --steps dispatches between two barrier+synchronize brackets (the
 contract).  Because a short region is mostly pipeline fill and drain (20 steps = 2 ms), the same loop is also run
 for >= 3 s of wall time: `sustained` — before the contract's region, so that the region is measured on a device at its
-steady clocks (the metric is a steady-state rate; out of idle the shader clock needs milliseconds to come up).  Further objects: `roofline` (integer-VALU bound; SURVEY.md §8(d) yardstick
-re-based on measured issue rates; chip-level fraction from wall time, the kernel's lone-launch rate from a
-frames=1 pass timed with HIP events, and the issue-side counters VALU-busy / instructions per key from the
-committed PMC pass under profiles/), `other_configs` (the other single-GPU BASELINE configurations and modes,
->= 1 s each), `time_to_first_match`, and `cpu_baseline` (the CPU oracle — a port of the reference's rayon path —
-on this box's cores; rank 0, N=1 only).
+steady clocks (the metric is a steady-state rate; out of idle the shader clock needs milliseconds to come up).  The region's
+scalars do not depend on how many dispatches that leg made: the region starts at the step after the warm-up, so the
+same arguments give the same inputs in every run.  `roofline` (integer-VALU bound; SURVEY.md §8(d) yardstick re-based on
+measured issue rates; chip-level fraction from wall time and the issue-side counters VALU-busy / instructions per key
+from the committed PMC pass under profiles/) is computed from the region and those files, without runs of its own.
+
+A plain run does only that.  `--full` adds what takes runs of its own: the roofline's per-launch figures (HIP-event
+durations of overlapped launches, and the kernel's lone-launch rate from a frames=1 pass), `other_configs` (the other
+single-GPU BASELINE configurations and modes, >= 1 s each), `time_to_first_match`, `cpu_baseline` (the CPU oracle — a
+port of the reference's rayon path — on this box's cores; these four at rank 0, N=1 only) and the in-process
+multi-device leg `in_process_multi` (N > 1, or a box with several GPUs).
+
+`--dump-outputs DIR` writes what a caller of the timed path receives from the region's LAST step, as .npy files in DIR
+(rank 0's step when N > 1): index.npy (the key offsets within the step's batch of the match records, float64),
+payload.npy (their hash160 / x-only key bytes, float32, one row per record) and counts.npy ([matches found, keys
+tested], float64).  A step without a device filter (dump mode) hands over every key's payload: a fixed sample of
+DUMP_SAMPLE_ROWS of them (seeded) is written instead.  That last wait copies the records out inside the region (tens of
+microseconds of host time); a run without the option waits as before.
 """
 import argparse
 import hashlib
@@ -168,9 +180,10 @@ class Pipeline:
         # copy through ctypes) and inside wait calls (blocked on the frame's stream + the return)
         self.host_dispatch_s = self.host_wait_s = 0.0
 
-    def run_steps(self, n_steps, collect=False, host_times=False):
+    def run_steps(self, n_steps, collect=False, host_times=False, fetch_last=False):
         """Exactly n_steps dispatches, all completed on return.  -> (candidates, [seq_bwd ms]).  host_times: also sum the
-        wall time spent inside the dispatch and the wait calls (two clock reads per call, ~0.1 us each)."""
+        wall time spent inside the dispatch and the wait calls (two clock reads per call, ~0.1 us each).  fetch_last: the
+        last step's wait also hands over its records (GpuRunner.await_result), kept in self.last_result."""
         r, F = self.r, self.f
         cand, kms, issued, done, fi, fw = 0, [], 0, 0, 0, 0
         first = self.next_step
@@ -189,7 +202,11 @@ class Pipeline:
         while done < n_steps:
             if host_times:
                 t = clock()
-            n, _ = r.wait(fw)
+            if fetch_last and done == n_steps - 1:
+                self.last_result = r.await_result(fw)
+                n = self.last_result[1]
+            else:
+                n, _ = r.wait(fw)
             if host_times:
                 t_done = clock()
                 tw += t_done - t
@@ -439,6 +456,27 @@ def host_roofline(strings_per_s, cores):
             "note": "Base58Check + DFA per string on the host's worker pool: 2 x 263 ns SHA-256 + ~0.2 us per core (profiles/r04_permissive.txt)"}
 
 
+DUMP_SAMPLE_ROWS = 1 << 16     # dump-mode rows written by --dump-outputs (2^16 x 32 B x 4 = 8 MB at most)
+
+
+def dump_outputs(out_dir, last_result, payload_bytes):
+    """--dump-outputs: GpuRunner.await_result's view of the region's last step -> out_dir/{index,payload,counts}.npy."""
+    import random
+    import numpy as np
+    recs, found, tested = last_result
+    if isinstance(recs, (bytes, bytearray)):    # dump mode: every key's payload, in key order
+        rows = np.frombuffer(recs, dtype=np.uint8).reshape(-1, payload_bytes)
+        index = np.array(sorted(random.Random(42).sample(range(len(rows)), min(DUMP_SAMPLE_ROWS, len(rows)))), dtype=np.int64)
+        payload = rows[index]
+    else:
+        index = np.array([i for i, _ in recs], dtype=np.int64)
+        payload = np.frombuffer(b"".join(p for _, p in recs), dtype=np.uint8).reshape(-1, payload_bytes)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "index.npy"), index.astype(np.float64))
+    np.save(os.path.join(out_dir, "payload.npy"), payload.astype(np.float32))
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([found, tested], dtype=np.float64))
+
+
 def parse_cpulist(text):
     """'0-15,64-79' -> {0..15, 64..79} (sysfs cpulist format)."""
     cpus = set()
@@ -626,14 +664,19 @@ def main():
     ap.add_argument("--endo", action="store_true", help="profiling aid: run the legs on a VGEN_FLAG_ENDO context (six keys per curve "
                                                         "point; NOT the BASELINE configuration, and said so in config.workload)")
     ap.add_argument("--sustained-seconds", type=float, default=3.0, help="wall time of the `sustained` leg (0 = skip)")
-    ap.add_argument("--no-other-configs", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the legs beside the headline figure: per-launch roofline figures, other_configs, "
+                                                        "time_to_first_match, cpu_baseline and the in-process multi-device leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step handed over as DIR/*.npy")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip other_configs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-numa-pin", action="store_true", help="leave the CPU affinity alone (default: every rank pins itself to the cores of its GPU's NUMA node)")
-    ap.add_argument("--multi-leg-seconds", type=float, default=3.0, help="wall time of the in-process vgen_scan_multi leg over all visible devices "
-                                                                         "(N > 1, or N = 1 on a multi-GPU box; 0 = skip)")
+    ap.add_argument("--multi-leg-seconds", type=float, default=None, help="wall time of the in-process vgen_scan_multi leg over all visible devices "
+                                                                          "(N > 1, or N = 1 on a multi-GPU box; default 3 with --full, else 0 = skip)")
     ap.add_argument("--multi-leg-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--multi-leg-cpus", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.multi_leg_seconds is None:
+        args.multi_leg_seconds = 3.0 if args.full else 0.0
 
     if args.multi_leg_child:
         if args.multi_leg_cpus:
@@ -646,6 +689,8 @@ def main():
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     # --gpus N is the number of ranks, one per GPU.  Under a launcher (torch.distributed.run sets WORLD_SIZE) the two must
     # agree; without one, N > 1 makes this process the launcher: it starts the N ranks as a CHILD (nothing here has
     # touched HIP or imported torch yet — never an exec of a process that has), relays rank 0's single JSON line and
@@ -752,6 +797,7 @@ def main():
     # ---- the contract's --warmup untimed steps ----
     pipe.run_steps(args.warmup)
     barrier()
+    region_first = pipe.next_step
 
     # ---- the same loop for >= 3 s of wall time.  It runs between the warm-up and the contract's region (nothing but
     # the barrier separates it from the region): BASELINE.json's metric is a
@@ -777,6 +823,13 @@ def main():
             shader_mhz = pipe.clk_cycles / pipe.clk_ticks * 100.0
         sustained = {"value": round(n_total * N * K6 / dt_s / 1e6, 2), "unit": "Mkeys/sec", "seconds": round(dt_s, 3),
                      "dispatches": n_total, "frames_in_flight": F}
+        # The leg stops on the clock, and the region's scalars must not depend on where it stopped: the walk steps back and
+        # re-enters at region_first.  The re-entry steps are untimed set-up: after a jump the host's incremental base points
+        # (host_seq_points) take two dispatches to find the stride and refill their look-ahead, which the region must not pay.
+        re_entry = max(F, 3)
+        pipe.next_step = region_first - re_entry
+        pipe.run_steps(re_entry)
+        assert pipe.next_step == region_first
 
     # ---- the contract's timed region: exactly --steps dispatches between two barrier + synchronize brackets ----
     # Opening bracket: barrier + synchronize, then every rank reads the clock.  Closing bracket: the rank's own
@@ -796,7 +849,7 @@ def main():
         while time.perf_counter() < t_go:
             pass
     t0 = time.perf_counter()
-    cand, _ = pipe.run_steps(args.steps, host_times=True)
+    cand, _ = pipe.run_steps(args.steps, host_times=True, fetch_last=args.dump_outputs is not None)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     barrier()
@@ -852,21 +905,22 @@ def main():
     # the dominant kernel (seq_bwd_kernel) does everything except the per-lane prefix products of
     # seq_fwd_kernel (half an F_p multiplication per key: 74 imul + 60 iop per multiplication)
     w_bwd = None if w_key is None else w_key - (74 * R_MUL + 60) // 2 / K6
-    # HIP-event durations of seq_bwd launches while the frames overlap (informational), from a short run of their own
+    # HIP-event durations of seq_bwd launches while the frames overlap (informational, --full), from a short run of their own
     avg_ms = in_flight = None
-    try:
-        rt = vg.GpuRunner(batch_size=args.batch, fmt=fmt, device=local_rank, frames=args.frames, timing=True, endo=args.endo)
-        rt.set_filter(pat if pat.device_kind != 0 else None)
-        pt = Pipeline(rt, seed_key(42, 0), world, rank)
-        pt.run_steps(2 * F)
-        t_ov = time.perf_counter()
-        _, kms = pt.run_steps(max(64, 16 * F), collect=True)
-        elapsed_ov = time.perf_counter() - t_ov
-        rt.close()
-        avg_ms = round(sum(kms) / len(kms), 4)
-        in_flight = round(sum(kms) * 1e-3 / elapsed_ov, 2)
-    except Exception:   # noqa: BLE001  (informational only)
-        pass
+    if args.full:
+        try:
+            rt = vg.GpuRunner(batch_size=args.batch, fmt=fmt, device=local_rank, frames=args.frames, timing=True, endo=args.endo)
+            rt.set_filter(pat if pat.device_kind != 0 else None)
+            pt = Pipeline(rt, seed_key(42, 0), world, rank)
+            pt.run_steps(2 * F)
+            t_ov = time.perf_counter()
+            _, kms = pt.run_steps(max(64, 16 * F), collect=True)
+            elapsed_ov = time.perf_counter() - t_ov
+            rt.close()
+            avg_ms = round(sum(kms) / len(kms), 4)
+            in_flight = round(sum(kms) * 1e-3 / elapsed_ov, 2)
+        except Exception:   # noqa: BLE001  (informational only)
+            pass
     chip = None if w_key is None else value * 1e6 / world * w_key / 1e12
     traffic = None
     pmc = {}
@@ -955,7 +1009,7 @@ def main():
                                 "start: after the opening barrier + synchronize, at an instant the ranks agreed on (rank 0's now + 3 ms, broadcast; "
                                 "each rank spins until it, so the barrier's uneven release does not count as work time); finish: after the rank's "
                                 "closing synchronize; the closing barrier follows the clock"}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # the kernel alone: frames = 1, so every launch has the chip to itself (one wave per SIMD), HIP events
         # recorded on the launch's own stream immediately before and after seq_bwd_kernel
         try:
@@ -997,7 +1051,7 @@ def main():
     runner.close()
     if multi_leg is not None:
         out["in_process_multi"] = multi_leg
-    if rank == 0 and world == 1 and not args.no_other_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_other_configs:
         sec = 1.0
         # every auxiliary leg stands alone: a failure there is recorded in its entry and never costs the headline line
         def leg(fn, *a, **kw):
@@ -1030,7 +1084,7 @@ def main():
         oc += leg(wide_table_configs, vg, args.batch, min(F, 8), local_rank, sec)
         oc += leg(dump_mode_configs, vg, args.batch, local_rank, sec)
         out["other_configs"] = oc
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             os.sched_setaffinity(0, affinity0)      # the CPU baseline is the whole box's cores, not this rank's socket
             out["cpu_baseline"] = cpu_baseline(args.format, args.pattern, args.ci)
@@ -1039,6 +1093,8 @@ def main():
                                    "error": f"{type(e).__name__}: {e}"}
     if world > 1:
         dist.destroy_process_group()
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, pipe.last_result, runner.payload_bytes)
     if rank == 0:
         if real_stdout is not None:
             sys.stdout.flush()

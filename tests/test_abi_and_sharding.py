@@ -330,7 +330,7 @@ def test_bench_two_rank_rehearsal_prints_one_contract_line():
     """bench.py's N>1 path (torchrun, gloo barrier / max over ranks, batch striping) run for real: two ranks
     sharing the one GPU of the test box (VGEN_BENCH_REHEARSE=1), rank 0 prints the single JSON line."""
     import json
-    out = _torchrun(os.path.join(ROOT, "bench.py"), ["--gpus", "2", "--steps", "64", "--warmup", "8", "--sustained-seconds", "0.3", "--multi-leg-seconds", "1"],
+    out = _torchrun(os.path.join(ROOT, "bench.py"), ["--gpus", "2", "--steps", "64", "--warmup", "8", "--sustained-seconds", "0.3", "--full", "--multi-leg-seconds", "1"],
                     29521, env_extra={"VGEN_BENCH_REHEARSE": "1"})
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.strip().splitlines()
@@ -405,6 +405,36 @@ def test_bench_plain_gpus_2_prints_n_gpus_2():
         # sit on different devices — here both were given the same one
         out = _bench(args, {"HIP_VISIBLE_DEVICES": "0"})
         assert out.returncode != 0 and out.stdout.strip() == "" and "the ranks sit on 1 device(s)" in out.stderr, out.stderr[-1500:]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_records(tmp_path):
+    """`bench.py --dump-outputs DIR`: the match records of the region's last step, the same in two runs whose sustained legs
+    differ in length (the region's scalars follow the warm-up, not the clock), and exactly the oracle's matches of that
+    step's 2^20 keys."""
+    import json
+    import numpy as np
+    import bench
+    from oracle import pyoracle as vo
+    frames, warmup, steps, n = 4, 2, 6, 1 << 20
+    got = []
+    for i, sustained in enumerate(("0.2", "0.5")):
+        out = _bench(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--frames", str(frames), "--sustained-seconds", sustained,
+                      "--dump-outputs", str(tmp_path / str(i))], timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads(out.stdout.strip().splitlines()[-1])
+        assert d["steps"] == steps and "other_configs" not in d and "cpu_baseline" not in d
+        got.append({k: np.load(tmp_path / str(i) / f"{k}.npy") for k in ("index", "payload", "counts")})
+    for k in ("index", "payload", "counts"):
+        assert np.array_equal(got[0][k], got[1][k]), k
+    index, payload, counts = got[0]["index"], got[0]["payload"], got[0]["counts"]
+    assert index.dtype == np.float64 and payload.dtype == np.float32 and payload.shape == (len(index), 20)
+    assert counts.tolist() == [len(index), n]
+    start = bench.batch_key(bench.seed_key(42, 0), frames + warmup + steps - 1, 1, 0, n)     # set-up F steps, the warm-up, the region
+    ref = vo.scan_range(vo.FMT_P2PKH, "^1Cat", start, start + n - 1, count=10**9, threads=bench.usable_cores())
+    assert [int(m["hex"], 16) - start for m in ref["matches"]] == index.astype(np.int64).tolist()
+    for i, row in zip(index.astype(np.int64), payload.astype(np.uint8)):
+        assert row.tobytes() == vo.payload(vo.FMT_P2PKH, start + int(i))
 
 
 def test_cli_warns_about_impossible_patterns_before_touching_the_device():

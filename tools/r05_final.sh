@@ -5,7 +5,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gputests.txt 2>&1 || 
 tail -2 $O/gputests.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -1 $O/smoke.txt
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 python - <<'PY'
 import json
 for f in ("bench_driver_args","bench"):

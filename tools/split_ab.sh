@@ -16,7 +16,7 @@ for R in 1 2; do
 done
 for SP in 1 0 1 0; do
   echo "== bench --steps 20 --warmup 5, VGEN_SPLIT=$SP"
-  VGEN_SPLIT=$SP python bench.py --gpus 1 --steps 20 --warmup 5 --no-other-configs --no-cpu-baseline 2>/dev/null | python -c "
+  VGEN_SPLIT=$SP python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-other-configs --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('value', d['value'], 'sustained', d['sustained']['value'], 'lone', d['roofline'].get('lone_launch',{}).get('avg_launch_ms'), 'ttfm', d.get('time_to_first_match'))
