@@ -199,18 +199,44 @@ int vgen_get_memory(const vgen_ctx *ctx, vgen_memory_info *out);
  * (pattern.rs:22-24,32-33). */
 int vgen_filter_compile(const char *pattern, int case_insensitive, uint32_t format, vgen_filter **out);
 void vgen_filter_free(vgen_filter *f);
-/* Pattern::matches (pattern.rs:43-45): unanchored regex search over the address string. 1 / 0. */
+/* Pattern::matches (pattern.rs:43-45): unanchored regex search over the address string. 1 / 0.  On a pattern list: any
+ * of its patterns. */
 int vgen_filter_matches(const vgen_filter *f, const char *address);
 /* How the device evaluates this filter: 0 = every key is reported to the host (no usable
  * prefilter; reference-equivalent host filtering), 1 = hash160 range test (Base58 prefixes),
  * 2 = masked-bits test (Bech32 / hex prefixes and suffixes), 3 = match-all, 4 = the pattern's whole DFA runs on the
- * device over the encoded address (unanchored patterns, Base58 suffixes). */
+ * device over the encoded address (unanchored patterns, Base58 suffixes), 5 = pattern list: the payloads stay on the
+ * device and are looked up in a table of intervals of their top 64 bits (vgen_filter_compile_list). */
 int vgen_filter_device_kind(const vgen_filter *f);
 /* Size in bytes of the automaton a kind-4 filter stages into LDS (at most 48 KiB; 0 for the other kinds).  With the
  * product tree (and, on a VGEN_FLAG_ENDO context of the uncompressed / Ethereum formats, the parked y coordinate)
  * beside it a workgroup must stay within 64 KiB of LDS: an ENDO dispatch whose automaton does not leave room for the
  * parked coordinate tests the plain keys only (vgen_wait then reports keys_tested = batch_size for it). */
 int vgen_filter_dfa_bytes(const vgen_filter *f);
+
+/* ---- pattern lists (VanitySearch -i / vanitygen -f: many patterns, one scan) ----------------------------------------
+ *
+ * A pattern list is text with one pattern per line ("\n" or "\r\n"); empty lines and lines starting with '#' are skipped
+ * but count for line numbers.  Pattern i is the i-th pattern line, from 0.  Each line has vgen_filter_compile's syntax; one
+ * case flag and one format apply to the whole list.  A list takes the patterns whose matches are ranges of the big-endian
+ * payload: start-anchored prefixes, classes and case-insensitivity included (Base58: up to 4096 hash160 ranges per pattern;
+ * Bech32 / hex: leading data symbols).  Suffixes, unanchored patterns, constraints on trailing symbols or the checksum,
+ * patterns that match every address or none, duplicate lines and an empty list are VGEN_E_PATTERN, with
+ * vgen_last_error(NULL) = "line N: reason"; such patterns still run alone through vgen_filter_compile.  At most 2^20
+ * patterns per list (100 000 five-character P2PKH prefixes compile in 1.8 s).
+ * The result is a vgen_filter of device kind 5 (vgen_filter_dfa_bytes 0): vgen_set_filter + vgen_dispatch* + vgen_wait work
+ * as for any filter, the records being candidates (a superset the host confirms with vgen_filter_which).  The device
+ * dumps the payloads into a device-only buffer of the frame (20 B per key, x 6 on a VGEN_FLAG_ENDO context, 32 B for P2TR;
+ * counted in vgen_memory_info.mode_bytes, allocated by vgen_set_filter) and two kernels look them up and compact the hits
+ * into the frame's match ring; every frame can be used. */
+int vgen_filter_compile_list(const char *patterns, int case_insensitive, uint32_t format, vgen_filter **out);
+/* Patterns in the filter: a list's count, 1 for a single pattern. */
+int vgen_filter_pattern_count(const vgen_filter *f, uint32_t *n);
+/* Text of pattern `index` (NUL-terminated; VGEN_E_INVALID when cap is too small).  Returns the length. */
+int vgen_filter_pattern(const vgen_filter *f, uint32_t index, char *out, size_t cap);
+/* Every pattern index the address satisfies, ascending: up to cap into indices, the full count into *n.  A single-pattern
+ * filter answers {0} or {}.  On a list, an address that does not decode under the list's format satisfies nothing. */
+int vgen_filter_which(const vgen_filter *f, const char *address, uint32_t *indices, uint32_t cap, uint32_t *n);
 /* Pattern::validate_charset(format) (src/pattern.rs:49-177): the characters of `pattern` that can never
  * occur in an address of `format` (literals outside classes; members of non-negated classes with no
  * valid member), in order of first appearance.  Writes up to cap-1 characters + NUL into `out` and the
@@ -425,6 +451,20 @@ int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_config *cfg, v
  * and the first failure's status — with out still filled, complete = 0 — when no context was left to do so. */
 int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const vgen_scan_config *cfg,
                     vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out);
+/* A scan for a pattern list (vgen_filter_compile_list) over one or several contexts, in every mode vgen_scan /
+ * vgen_scan_multi have (seeded or random base walk, start / end, VGEN_FLAG_ENDO, VGEN_SCAN_RANDOM_KEYS, checkpoints,
+ * striping and failure take-over over n_ctx contexts).  cfg->format must be the list's; cfg->case_insensitive is ignored
+ * (the list carries it).  A key is reported once and counts toward every pattern it satisfies; once a pattern has
+ * per_pattern matches, a key that satisfies only such patterns is not reported (per_pattern = 0: no per-pattern bound).
+ * The scan ends when every pattern has per_pattern matches, at cfg->count results in total, at the end of the range or on
+ * the stop flag.  Results come in vgen_scan's order — batches in order, keys ascending within a batch — so a seeded scan
+ * is reproducible and its matches of pattern i are the first keys of the walk that satisfy it (vgen_filter_which gives
+ * the indices of a result).  A checkpoint's identity includes the list (a digest of its pattern texts, the case flag and
+ * the format): a checkpoint written for another list is VGEN_E_INVALID.  (With n_ctx > 1 and a checkpoint, the matches of
+ * earlier runs count first, in the order they were recorded.) */
+int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter *list, uint64_t per_pattern,
+                   const vgen_scan_config *cfg, vgen_progress_cb cb, void *user, const volatile int32_t *stop,
+                   vgen_scan_result *out);
 void vgen_scan_result_free(vgen_scan_result *r);
 
 #ifdef __cplusplus

@@ -149,6 +149,14 @@ _L.vgen_scan.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(_ScanC
 _L.vgen_scan_multi.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_char_p,
                                ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                ctypes.POINTER(_ScanResult)]
+_L.vgen_filter_compile_list.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p)]
+_L.vgen_filter_pattern_count.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+_L.vgen_filter_pattern.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]
+_L.vgen_filter_which.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
+                                 ctypes.POINTER(ctypes.c_uint32)]
+_L.vgen_scan_list.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint64,
+                              ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+                              ctypes.POINTER(_ScanResult)]
 _L.vgen_scan_result_free.argtypes = [ctypes.POINTER(_ScanResult)]
 _L.vgen_scan_result_free.restype = None
 
@@ -285,6 +293,59 @@ class Pattern:
             self._h = None
 
 
+class PatternList:
+    """A list of patterns matched in one scan (vgen_filter_compile_list): one pattern per line of `patterns` (or an
+    iterable of lines), start-anchored prefixes only; device kind 5.  Raises VgenError with "line N: reason" otherwise."""
+
+    def __init__(self, patterns, case_insensitive: bool = False, fmt: AddressFormat = AddressFormat.P2pkh):
+        text = patterns if isinstance(patterns, str) else "\n".join(patterns)
+        self.case_insensitive, self.format = case_insensitive, AddressFormat(int(fmt))
+        h = ctypes.c_void_p()
+        _check(_L.vgen_filter_compile_list(text.encode(), int(case_insensitive), int(fmt), ctypes.byref(h)))
+        self._h = h
+        n = ctypes.c_uint32()
+        _check(_L.vgen_filter_pattern_count(h, ctypes.byref(n)))
+        self._n = n.value
+
+    def __len__(self) -> int:
+        return self._n
+
+    def pattern(self, index: int) -> str:
+        """Text of pattern `index` (what the command line prints in a result's `pattern` field)."""
+        buf = ctypes.create_string_buffer(4096)
+        rc = _L.vgen_filter_pattern(self._h, index, buf, 4096)
+        _check(rc)
+        return buf.value.decode()
+
+    def which(self, address: str) -> List[int]:
+        """vgen_filter_which: every pattern index the address satisfies, ascending."""
+        cap = 64
+        while True:
+            arr, n = (ctypes.c_uint32 * cap)(), ctypes.c_uint32()
+            _check(_L.vgen_filter_which(self._h, address.encode(), arr, cap, ctypes.byref(n)))
+            if n.value <= cap:
+                return list(arr[:n.value])
+            cap = n.value
+
+    def matches(self, address: str) -> bool:
+        return _L.vgen_filter_matches(self._h, address.encode()) == 1
+
+    @property
+    def device_kind(self) -> int:
+        return _L.vgen_filter_device_kind(self._h)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _L.vgen_filter_free(self._h)
+            self._h = None
+
+
+@dataclass
+class ListMatch(GeneratedAddress):
+    """A result of scan_list: the address and the lowest index of the patterns it satisfies."""
+    pattern_index: int = -1
+
+
 @dataclass
 class ProviderResult:
     """ProviderResult (src/provider.rs:6-10)."""
@@ -394,7 +455,8 @@ class GpuRunner:
 
     __del__ = close
 
-    def set_filter(self, pattern: Optional[Pattern]):
+    def set_filter(self, pattern):
+        """A Pattern, a PatternList (candidates: a superset the host confirms with which()), or None for dump mode."""
         _check(_L.vgen_set_filter(self._h, pattern._h if pattern else None), self._h)
         self._pattern = pattern
 
@@ -485,13 +547,7 @@ class GpuRunner:
         return ms.value
 
 
-def scan_gpu_with_runner(pattern: str, config: ScanConfig, runner,
-                         progress_cb: Optional[Callable[[int], None]] = None, stop=None, force_multi: bool = False) -> ScanResult:
-    """scan_gpu_with_runner (src/gpu.rs:920-926).  `stop` is an optional ctypes.c_int32 flag.
-    `runner` may be a list of GpuRunners (one per GPU): the batches are then striped over them
-    (vgen_scan_multi; force_multi: also for a list of one)."""
-    runners = list(runner) if isinstance(runner, (list, tuple)) else [runner]
-    runner = runners[0]
+def _scan_config(config: ScanConfig) -> _ScanConfig:
     c = _ScanConfig()
     c.struct_size = ctypes.sizeof(_ScanConfig)
     c.format = int(config.format)
@@ -509,6 +565,45 @@ def scan_gpu_with_runner(pattern: str, config: ScanConfig, runner,
         c.checkpoint_interval_ms = config.checkpoint_interval_ms
     c.flags = SCAN_RANDOM_KEYS if config.random_keys else 0
     c.table_bits_max = config.table_bits_max
+    return c
+
+
+def scan_list(plist: PatternList, config: ScanConfig, runner, per_pattern: int = 1,
+              progress_cb: Optional[Callable[[int], None]] = None, stop=None) -> ScanResult:
+    """vgen_scan_list: one scan for every pattern of `plist` over one GpuRunner or a list of them.  config.format must be
+    the list's; config.count (None = unbounded) caps the results in total, per_pattern (0 = unbounded) per pattern.
+    The matches are ListMatch records in the scan's order, each with the lowest index of the patterns it satisfies."""
+    runners = list(runner) if isinstance(runner, (list, tuple)) else [runner]
+    c = _scan_config(config)
+    res = _ScanResult()
+    cb = _PROGRESS(lambda ops, _u: progress_cb(ops)) if progress_cb else ctypes.cast(None, _PROGRESS)
+    stop_p = ctypes.byref(stop) if stop is not None else None
+    arr = (ctypes.c_void_p * len(runners))(*[r._h for r in runners])
+    rc = _L.vgen_scan_list(arr, len(runners), plist._h, per_pattern, ctypes.byref(c), cb, None, stop_p, ctypes.byref(res))
+    out = ScanResult(operations=res.operations, elapsed_secs=res.elapsed_secs,
+                     resumed_operations=res.resumed_operations, complete=bool(res.complete), failed_shards=res.failed_shards)
+    for i in range(res.n_matches):
+        g = res.matches[i]
+        a = g.address.decode()
+        w = plist.which(a)
+        out.matches.append(ListMatch(a, g.wif.decode(), g.hex.decode(), AddressFormat(g.format), w[0] if w else -1))
+    _L.vgen_scan_result_free(ctypes.byref(res))
+    if rc < 0:
+        msg = _L.vgen_last_error(runners[0]._h)
+        err = VgenError(rc, msg.decode() if msg else "")
+        err.partial = out
+        raise err
+    return out
+
+
+def scan_gpu_with_runner(pattern: str, config: ScanConfig, runner,
+                         progress_cb: Optional[Callable[[int], None]] = None, stop=None, force_multi: bool = False) -> ScanResult:
+    """scan_gpu_with_runner (src/gpu.rs:920-926).  `stop` is an optional ctypes.c_int32 flag.
+    `runner` may be a list of GpuRunners (one per GPU): the batches are then striped over them
+    (vgen_scan_multi; force_multi: also for a list of one)."""
+    runners = list(runner) if isinstance(runner, (list, tuple)) else [runner]
+    runner = runners[0]
+    c = _scan_config(config)
     res = _ScanResult()
     cb = _PROGRESS(lambda ops, _u: progress_cb(ops)) if progress_cb else ctypes.cast(None, _PROGRESS)
     stop_p = ctypes.byref(stop) if stop is not None else None

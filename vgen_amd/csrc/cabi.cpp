@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
 
 #include "../../include/vgen_hip.h"
 #include "host/encode.h"
@@ -96,7 +97,42 @@ void vgen_filter_free(vgen_filter *f) { delete f; }
 
 int vgen_filter_matches(const vgen_filter *f, const char *address) {
     if (!f || !address) return VGEN_E_INVALID;
+    if (f->list) return vg::filter_accepts(*f, address, nullptr) ? 1 : 0;
     return f->dfa.is_match(address) ? 1 : 0;
+}
+
+int vgen_filter_compile_list(const char *patterns, int case_insensitive, uint32_t format, vgen_filter **out) {
+    if (!patterns || !out) return VGEN_E_INVALID;
+    vgen_filter *f = new vgen_filter();
+    std::string err;
+    if (!vg::filter_compile_list(patterns, case_insensitive != 0, format, *f, err)) {
+        g_last_error = err;
+        delete f;
+        return VGEN_E_PATTERN;
+    }
+    *out = f;
+    return VGEN_OK;
+}
+
+int vgen_filter_pattern_count(const vgen_filter *f, uint32_t *n) {
+    if (!f || !n) return VGEN_E_INVALID;
+    *n = f->list ? (uint32_t)f->list->patterns.size() : 1u;
+    return VGEN_OK;
+}
+
+int vgen_filter_pattern(const vgen_filter *f, uint32_t index, char *out, size_t cap) {
+    if (!f) return VGEN_E_INVALID;
+    if (f->list ? index >= f->list->patterns.size() : index != 0) return VGEN_E_INVALID;
+    return copy_out(f->list ? f->list->patterns[index] : f->pattern, out, cap);
+}
+
+int vgen_filter_which(const vgen_filter *f, const char *address, uint32_t *indices, uint32_t cap, uint32_t *n) {
+    if (!f || !address || !n || (cap && !indices)) return VGEN_E_INVALID;
+    std::vector<uint32_t> w;
+    vg::filter_which(*f, address, nullptr, w);
+    *n = (uint32_t)w.size();
+    for (uint32_t i = 0; i < w.size() && i < cap; i++) indices[i] = w[i];
+    return VGEN_OK;
 }
 
 int vgen_filter_device_kind(const vgen_filter *f) { return f ? (int)f->dev.kind : VGEN_E_INVALID; }

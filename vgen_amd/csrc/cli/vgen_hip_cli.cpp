@@ -34,6 +34,9 @@ struct Opts {
     std::string cmd, pattern, format = "p2pkh", output = "text", file, range, key, address, devices = "0", checkpoint, provider_table;
     bool has_pattern = false, ignore_case = false, quiet = false, json = false, no_gpu = false;
     uint64_t count = 1, repeat = 1, seed = 0;
+    std::string patterns_file;                // --patterns-file: one pattern per line, one scan (vgen_scan_list)
+    bool has_patterns_file = false, count_given = false;
+    uint64_t per_pattern = 1;                 // --per-pattern (0 = unbounded)
     bool no_endo = false;
     bool random_keys = false;
     uint32_t batch = 1u << 20, frames = 12;   // twelve frames own twelve hardware queues (runtime.cpp)
@@ -197,6 +200,9 @@ void usage() {
             "                                           the reference's CPU path, src/scanner.rs:118-169 —, six keys per draw unless\n"
             "                                           --no-endo; ~3x slower than the walk)\n"
             "                    PATTERN may be a provider pattern boha:b1000:N [-l PREFIX_LENGTH] [--provider-table CSV]\n"
+            "  vgen-hip generate --patterns-file FILE [--per-pattern N] ...   (instead of -p: one start-anchored prefix per line,\n"
+            "                    one scan; N results per pattern (default 1, 0 = unbounded), -c caps the total (default: none);\n"
+            "                    each result's pattern field is the lowest-index line it satisfies.  range takes it too)\n"
             "  vgen-hip range (--range START:END | --puzzle P) [-p PATTERN] [-f FORMAT] [-c COUNT (0 = whole range)] ...\n"
             "  vgen-hip estimate -p PATTERN [-f FORMAT] [-i]\n"
             "  vgen-hip verify -k WIF_OR_HEX [-a ADDRESS]\n"
@@ -217,7 +223,7 @@ Opts parse(int argc, char **argv) {
     static const char *const long_with_value[] = {"--pattern", "--format", "--count", "--output", "--file", "--gpu-batch-size", "--repeat",
                                                   "--seed", "--devices", "--frames", "--checkpoint", "--range", "--puzzle", "--key", "--address",
                                                   "--prefix-length", "--provider-table", "--threads", "--backend", "--cpu-batch-size", "--table-bits-max",
-                                                  "--mem-budget-gib"};
+                                                  "--mem-budget-gib", "--patterns-file", "--per-pattern"};
     static const char short_with_value[] = "pfcorkaltT";
     std::vector<std::string> args;
     bool next_is_value = false;
@@ -262,7 +268,9 @@ Opts parse(int argc, char **argv) {
         if (a == "-p" || a == "--pattern") { o.pattern = val(); o.has_pattern = true; }
         else if (a == "-f" || a == "--format") o.format = val();
         else if (a == "-i" || a == "--ignore-case") o.ignore_case = true;
-        else if (a == "-c" || a == "--count") o.count = strtoull(val().c_str(), nullptr, 10);
+        else if (a == "-c" || a == "--count") { o.count = strtoull(val().c_str(), nullptr, 10); o.count_given = true; }
+        else if (a == "--patterns-file") { o.patterns_file = val(); o.has_patterns_file = true; }
+        else if (a == "--per-pattern") o.per_pattern = strtoull(val().c_str(), nullptr, 10);
         else if (a == "-o" || a == "--output") o.output = val();
         else if (a == "--file") o.file = val();
         else if (a == "--gpu-batch-size") o.batch = (uint32_t)strtoul(val().c_str(), nullptr, 10);
@@ -435,14 +443,49 @@ void progress_clear(Progress &p) {
     p.shown = false;
 }
 
-int run_search(const Opts &o, const std::string &pattern, bool has_range, const uint8_t start[32], const uint8_t end[32]) {
+// --patterns-file: the list, compiled before any device is opened.  A provider pattern or an invalid line ends the program
+// (status 1) with its line number.
+vgen_filter *load_pattern_list(const Opts &o, int fmt) {
+    FILE *f = fopen(o.patterns_file.c_str(), "rb");
+    if (!f) die("cannot read patterns file '" + o.patterns_file + "'");
+    std::string text;
+    char buf[65536];
+    for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) text.append(buf, n);
+    fclose(f);
+    size_t pos = 0;
+    for (unsigned line = 1; pos < text.size(); line++) {
+        size_t e = text.find('\n', pos);
+        if (e == std::string::npos) e = text.size();
+        if (text.compare(pos, 5, "boha:") == 0)
+            die(o.patterns_file + ": line " + std::to_string(line) + ": provider patterns (boha:) cannot be part of a pattern list");
+        pos = e + 1;
+    }
+    vgen_filter *list = nullptr;
+    if (vgen_filter_compile_list(text.c_str(), o.ignore_case, (uint32_t)fmt, &list) != VGEN_OK)
+        die(o.patterns_file + ": " + vgen_last_error(nullptr));
+    return list;
+}
+
+// The text of the lowest-index pattern of `list` that `address` satisfies (a result's `pattern` field).
+std::string list_pattern_of(const vgen_filter *list, const char *address) {
+    uint32_t idx = 0, n = 0;
+    if (vgen_filter_which(list, address, &idx, 1, &n) != VGEN_OK || n == 0) return std::string();
+    char buf[4096];
+    return vgen_filter_pattern(list, idx, buf, sizeof buf) >= 0 ? std::string(buf) : std::string();
+}
+
+int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, const uint8_t start[32], const uint8_t end[32],
+               const vgen_filter *list = nullptr) {
+    const std::string &pattern = pattern_arg;
     if (o.no_gpu) die("--no-gpu: this build has no CPU scan path (the MI355X engine is the only backend)");
     const int fmt = format_id(o.format);
     // surface pattern errors before touching the device (Pattern::new, pattern.rs:21-33)
-    vgen_filter *probe = nullptr;
-    if (vgen_filter_compile(pattern.c_str(), o.ignore_case, (uint32_t)fmt, &probe) != VGEN_OK) die(vgen_last_error(nullptr));
-    vgen_filter_free(probe);
-    warn_impossible_pattern(pattern, o.ignore_case, fmt);
+    if (!list) {
+        vgen_filter *probe = nullptr;
+        if (vgen_filter_compile(pattern.c_str(), o.ignore_case, (uint32_t)fmt, &probe) != VGEN_OK) die(vgen_last_error(nullptr));
+        vgen_filter_free(probe);
+        warn_impossible_pattern(pattern, o.ignore_case, fmt);
+    }
 
     std::vector<int> devs = parse_devices(o.devices);
     std::vector<vgen_ctx *> ctxs;
@@ -469,6 +512,7 @@ int run_search(const Opts &o, const std::string &pattern, bool has_range, const 
     cfg.struct_size = sizeof cfg;
     cfg.format = (uint32_t)fmt;
     cfg.count = o.count == 0 ? UINT64_MAX : o.count;   // lib.rs:524
+    if (list && !o.count_given) cfg.count = UINT64_MAX;   // a list is bounded per pattern (--per-pattern); -c stays the total cap
     cfg.case_insensitive = o.ignore_case;
     cfg.seed = o.seed;
     cfg.table_bits_max = o.table_bits_max;
@@ -496,9 +540,11 @@ int run_search(const Opts &o, const std::string &pattern, bool has_range, const 
     for (uint64_t rep = 0; rep < (o.repeat ? o.repeat : 1) && !g_stop; rep++) {   // lib.rs:825-865
         vgen_scan_result res;
         prog.base = total_ops;
-        int rc = ctxs.size() == 1 ? vgen_scan(ctxs[0], pattern.c_str(), &cfg, show_progress ? progress_cb : nullptr, &prog, &g_stop, &res)
-                                  : vgen_scan_multi(ctxs.data(), (uint32_t)ctxs.size(), pattern.c_str(), &cfg, show_progress ? progress_cb : nullptr,
-                                                    &prog, &g_stop, &res);
+        int rc = list ? vgen_scan_list(ctxs.data(), (uint32_t)ctxs.size(), list, o.per_pattern, &cfg, show_progress ? progress_cb : nullptr,
+                                       &prog, &g_stop, &res)
+                 : ctxs.size() == 1 ? vgen_scan(ctxs[0], pattern.c_str(), &cfg, show_progress ? progress_cb : nullptr, &prog, &g_stop, &res)
+                                    : vgen_scan_multi(ctxs.data(), (uint32_t)ctxs.size(), pattern.c_str(), &cfg, show_progress ? progress_cb : nullptr,
+                                                      &prog, &g_stop, &res);
         progress_clear(prog);
         if (rc != VGEN_OK) die(vgen_last_error(ctxs[0]));
         // what the scan absorbed must not pass unseen: a device that failed (the others took its ranges over), a generator
@@ -527,6 +573,7 @@ int run_search(const Opts &o, const std::string &pattern, bool has_range, const 
         fprintf(w, "address,wif,private_key_hex,format,pattern,operations,elapsed_secs,rate\n");
     for (size_t idx = 0; idx < all.size(); idx++) {
         const vgen_generated &g = all[idx];
+        const std::string pattern = list ? list_pattern_of(list, g.address) : pattern_arg;
         if (o.output == "text") {
             fprintf(w, "=== Match %zu of %zu ===\n", idx + 1, all.size());
             fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nWIF     : %s\nHex     : %s\n", pattern.c_str(),
@@ -577,6 +624,32 @@ int main(int argc, char **argv) {
 
     Opts o = parse(argc, argv);
     signal(SIGINT, on_sigint);
+    if ((o.cmd == "generate" || o.cmd == "range") && o.has_patterns_file) {
+        if (o.has_pattern) die("the argument '--patterns-file' cannot be used with '--pattern'");
+        vgen_filter *list = load_pattern_list(o, format_id(o.format));
+        uint8_t start[32] = {0}, end[32] = {0};
+        if (o.cmd == "range") {
+            if (o.puzzle) {
+                if (o.puzzle < 1 || o.puzzle > 160) die("Puzzle number must be between 1 and 160");
+                const int sb = o.puzzle - 1;
+                start[31 - sb / 8] = (uint8_t)(1u << (sb % 8));
+                for (int b = 0; b < o.puzzle; b++) end[31 - b / 8] |= (uint8_t)(1u << (b % 8));
+            } else if (!o.range.empty()) {
+                size_t c = o.range.find(':');
+                if (c == std::string::npos || o.range.find(':', c + 1) != std::string::npos) die("Range must be in format START:END");
+                if (!parse_hex_key(o.range.substr(0, c), start)) die("Invalid start hex");
+                if (!parse_hex_key(o.range.substr(c + 1), end)) die("Invalid end hex");
+            } else {
+                die("Either --range or --puzzle must be specified");
+            }
+            bool start_zero = true;
+            for (int i = 0; i < 32; i++) start_zero = start_zero && start[i] == 0;
+            if (start_zero) start[31] = 1;
+        }
+        const int rc = run_search(o, std::string(), o.cmd == "range", start, end, list);
+        vgen_filter_free(list);
+        return rc;
+    }
     if (o.cmd == "generate") {
         if (!o.has_pattern) die("the following required arguments were not provided: --pattern <PATTERN>");
         uint8_t z[32] = {0};

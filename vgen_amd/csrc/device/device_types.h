@@ -22,7 +22,9 @@ enum : uint32_t {
     DEVF_RANGES = 1,     // any r:  lo_r <= H <= hi_r           (Base58 prefixes)
     DEVF_MASKED = 2,     // any t:  (H & mask_t) == value_t     (Bech32 / hex prefixes & suffixes)
     DEVF_ALL = 3,        // pattern accepts every address
-    DEVF_DFA = 4         // full match on the device: encode the address, walk the DFA (core/dfa_eval.h)
+    DEVF_DFA = 4,        // full match on the device: encode the address, walk the DFA (core/dfa_eval.h)
+    DEVF_LIST = 5        // pattern list: the payloads are dumped on the device and looked up in a table of intervals
+                         // (core/ptab_eval.h, DevPtab); not evaluated through DevFilter
 };
 
 constexpr uint32_t DEVF_MAX_TESTS = 64;
@@ -53,6 +55,19 @@ struct DevFilter {
     DevFilterTest tests[DEVF_MAX_TESTS];
 };
 
+// Pattern-list table (DEVF_LIST, core/ptab_eval.h): disjoint intervals [lo_j, hi_j] of the top 64 bits of the big-endian
+// payload, sorted, with a first level over the top `bits` bits: bit b of `bitmap` is set when bucket b meets an interval,
+// and offsets[b] is the first interval whose hi >= the bucket's first value (offsets[2^bits] = n).  Passed by value to the
+// list kernels; not part of DevFilter, whose layout every other kernel reads.
+struct DevPtab {
+    const uint32_t *bitmap;      // 2^bits bits
+    const uint32_t *offsets;     // 2^bits + 1 entries
+    const uint64_t *lo;          // n interval bounds
+    const uint64_t *hi;
+    uint32_t bits;               // 16 .. 24
+    uint32_t n;
+};
+
 // Match ring of one frame (device memory).  count may run past cap; records beyond cap are dropped.
 struct DevMatch {
     uint32_t index;
@@ -65,6 +80,21 @@ struct DevMatchHeader {
     uint32_t cap;
     uint32_t clk_cycles;   // running sums (mod 2^32) over the frame's seq_bwd launches, first wave of each launch:
     uint32_t clk_ticks;    // shader-clock cycles and 100 MHz ticks it ran for (kernels.hip: "shader-clock sample")
+};
+
+// Arguments of the two list kernels of one dispatch: the payloads the per-key kernel dumped (images x stride slots, the
+// first `count` of every image written), the hit mask (one bit per slot) and the frame's match ring.
+struct PtabArgs {
+    DevPtab tab;
+    const uint32_t *payloads;    // slot s at payloads + s * payload_words
+    unsigned long long *hits;    // images * stride / 64 words
+    DevMatchHeader *mhdr;
+    DevMatch *mrec;
+    uint32_t stride;             // slots per image (the context's batch size; a multiple of 8192)
+    uint32_t count;              // slots written per image (n of vgen_dispatch_keys, else stride)
+    uint32_t images;             // 6 on an endomorphism dispatch, else 1
+    uint32_t match_base;
+    uint32_t match_cap;
 };
 
 // Per-dispatch uniform points of the sequential kernel: Q_j = (k0 + N/2 - S/2 + j)*G and the

@@ -1859,3 +1859,107 @@ hipError_t launch_seq_bwd(int fmt, const SeqArgs &a, hipStream_t stream) {
 }
 
 }  // namespace vg
+
+// ---- pattern lists (DEVF_LIST) ----------------------------------------------------------------------------------
+// A list filter runs the per-key kernels above exactly as in dump mode, into a device-only payload buffer of the frame,
+// and then these two: a lookup of every written payload in the list's interval table (core/ptab_eval.h) into a hit mask
+// (one bit per slot, one plain 64-bit store per wave), and one workgroup that turns the mask into the frame's match
+// records in ascending index order.  Nothing else writes the ring during the dispatch, so neither needs an atomic.
+#include "../core/ptab_eval.h"
+
+namespace vg {
+
+template <int NW>
+__global__ void __launch_bounds__(256) ptab_lookup_kernel(const PtabArgs a) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;          // slot within the image (stride is a multiple of 256)
+    const size_t slot = (size_t)blockIdx.y * a.stride + i;  // image-major, as the dump is laid out
+    bool hit = false;
+    if (i < a.count) {
+        const u32 *p = a.payloads + slot * NW;
+        const u64 x = ptab_top64(p);
+        hit = ptab_find(a.tab, x) >= 0;
+        if (hit && x == 0) {   // the dump's "no key" mark (an invalid scalar) is an all-zero payload: never a candidate
+            u32 z = 0;
+#pragma unroll
+            for (int k = 2; k < NW; k++) z |= p[k];
+            hit = z != 0;
+        }
+    }
+    const unsigned long long m = __ballot(hit);
+    if ((threadIdx.x & 63u) == 0) a.hits[slot >> 6] = m;
+}
+
+constexpr int PTAB_COMPACT_WG = 1024;
+constexpr int PTAB_WORDS_PER_LANE = 16;   // mask words per thread and pass: one pass (one scan, two barriers) per 2^20 slots
+
+template <int NW>
+__global__ void __launch_bounds__(PTAB_COMPACT_WG) ptab_compact_kernel(const PtabArgs a) {
+    __shared__ u32 wave_sum[PTAB_COMPACT_WG / 64];
+    const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const u32 words = (u32)((size_t)a.images * a.stride / 64);
+    const u32 start = a.mhdr->count;   // the ring's running count: this dispatch's records follow it
+    u32 run = 0;                       // hits of the passes before this one (uniform)
+    for (u32 w0 = 0; w0 < words; w0 += PTAB_COMPACT_WG * PTAB_WORDS_PER_LANE) {
+        // this thread's PTAB_WORDS_PER_LANE consecutive words: threads in index order, words in index order within a thread
+        const u32 wb = w0 + threadIdx.x * PTAB_WORDS_PER_LANE;
+        unsigned long long m[PTAB_WORDS_PER_LANE];
+        u32 c = 0;
+#pragma unroll
+        for (int k = 0; k < PTAB_WORDS_PER_LANE; k++) {
+            m[k] = wb + k < words ? a.hits[wb + k] : 0ull;
+            c += (u32)__popcll(m[k]);
+        }
+        // exclusive prefix of c over the workgroup: within the wave, then over the waves' totals
+        u32 incl = c;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const u32 t = __shfl_up(incl, d, 64);
+            if (lane >= (u32)d) incl += t;
+        }
+        if (lane == 63) wave_sum[wave] = incl;
+        __syncthreads();
+        u32 before = 0, total = 0;
+#pragma unroll
+        for (u32 k = 0; k < PTAB_COMPACT_WG / 64; k++) {
+            const u32 s = wave_sum[k];
+            before += k < wave ? s : 0u;
+            total += s;
+        }
+        __syncthreads();   // (wave_sum is rewritten by the next pass)
+        u32 slot = start + run + before + incl - c - a.match_base;
+#pragma unroll
+        for (int k = 0; k < PTAB_WORDS_PER_LANE; k++) {
+            unsigned long long mm = m[k];
+            while (mm) {
+                const u32 b = (u32)(__ffsll((long long)mm) - 1);
+                mm &= mm - 1;
+                if (slot < a.match_cap) {
+                    const u32 index = (wb + k) * 64u + b;
+                    const u32 *p = a.payloads + (size_t)index * NW;
+                    DevMatch *r = a.mrec + slot;
+                    r->index = index;
+                    r->reserved = 0;
+#pragma unroll
+                    for (int q = 0; q < 8; q++) r->payload[q] = q < NW ? p[q] : 0u;   // (zero beyond the payload, as every filter kernel)
+                }
+                slot++;
+            }
+        }
+        run += total;
+    }
+    if (threadIdx.x == 0) a.mhdr->count = start + run;   // plain store: the only writer of the header in this dispatch
+}
+
+hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream) {
+    if (a.stride % 256 != 0 || a.count > a.stride || a.images == 0 || a.tab.bits < 1 || a.tab.bits > 24) return hipErrorInvalidValue;
+    const dim3 grid(a.stride / 256, a.images);
+    if (payload_words == 8) hipLaunchKernelGGL((ptab_lookup_kernel<8>), grid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((ptab_lookup_kernel<5>), grid, dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (payload_words == 8) hipLaunchKernelGGL((ptab_compact_kernel<8>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, a);
+    else hipLaunchKernelGGL((ptab_compact_kernel<5>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace vg

@@ -43,3 +43,9 @@ hipError_t launch_rtab_build(const RtabArgs &a, hipStream_t stream);
 // Enqueues the shader-clock probe: out[0] = shader-clock cycles, out[1] = 100 MHz ticks elapsed (>= ticks).
 hipError_t launch_clock_probe(unsigned long long *out, unsigned long long ticks, hipStream_t stream);
 }  // namespace vg
+
+namespace vg {
+// The two kernels of a pattern-list dispatch behind the per-key kernels (which dumped the payloads into a.payloads): lookup
+// of every written slot in the list's interval table into the hit mask, then compaction of the hits into the match ring.
+hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream);
+}  // namespace vg

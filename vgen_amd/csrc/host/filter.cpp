@@ -3,11 +3,15 @@
 
 #include "../core/dfa_eval.h"
 #include "../core/filter_eval.h"
+#include "../core/ptab_eval.h"
+#include "encode.h"
 
 #include <string.h>
 
 #include <algorithm>
+#include <map>
 #include <set>
+#include <unordered_map>
 #include <vector>
 
 namespace vg {
@@ -585,6 +589,346 @@ bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t 
         out.selectivity = -1.0;                   // unknown: the scanner adapts (ring overflow -> host filtering)
     }
     return true;
+}
+
+// ---- pattern lists ------------------------------------------------------------------------------------------------
+
+namespace {
+
+constexpr size_t LIST_MAX_RANGES = 4096;   // payload ranges of one pattern (a single pattern's prefilter takes DEVF_MAX_TESTS)
+
+struct Range64 {
+    uint64_t lo, hi;
+    uint32_t pat;
+};
+
+// top 64 bits of a 160-bit value held in a U256
+uint64_t top64_of160(const U256 &a) { return (a.w[1] >> 32) | (a.w[2] << 32); }
+
+const char *const NOT_PREFIX =
+    "is not a start-anchored prefix (a list takes patterns whose matches are ranges of the payload: suffixes, unanchored "
+    "patterns and constraints on later symbols or the checksum run alone through vgen_filter_compile)";
+
+// The top-64-bit ranges of one pattern, or a reason why it has none a list can use.
+bool list_ranges(const std::string &pattern, bool ci, uint32_t format, uint32_t index, std::vector<Range64> &out, std::string &why) {
+    Dfa d;
+    std::string err;
+    // Ethereum: the device sees the payload, not the EIP-55 casing: ranges of the case-folded language (the host confirms)
+    if (!regex_compile(pattern, ci || format == VGF_ETHEREUM, d, err)) {
+        why = err;
+        return false;
+    }
+    if (d.lazy) {
+        why = NOT_PREFIX;
+        return false;
+    }
+    const size_t first = out.size();
+    if (format == VGF_P2PKH || format == VGF_P2PKH_UNCOMPRESSED || format == VGF_P2SH_P2WPKH) {
+        if (d.match_now[0]) {
+            why = "matches every address";
+            return false;
+        }
+        std::vector<Prefix> prefixes;
+        if (!enumerate_prefixes(d, 0, B58, 40, 200000, prefixes)) {
+            why = NOT_PREFIX;
+            return false;
+        }
+        for (auto &p : prefixes)
+            if (!p.absorbing) {
+                why = NOT_PREFIX;
+                return false;
+            }
+        std::vector<Range> ranges;
+        for (auto &p : prefixes) prefix_to_ranges(p.s, format == VGF_P2SH_P2WPKH ? 0x05 : 0x00, ranges);
+        merge_ranges(ranges);
+        if (ranges.size() > LIST_MAX_RANGES) {
+            why = "needs more than " + std::to_string(LIST_MAX_RANGES) + " payload ranges";
+            return false;
+        }
+        double total = 0;
+        for (auto &r : ranges) total += to_double(sub(r.hi, r.lo)) + 1.0;
+        if (total / 1.4615016373309029e48 > 0.999999) {
+            why = "matches every address";
+            return false;
+        }
+        for (auto &r : ranges) out.push_back({top64_of160(r.lo), top64_of160(r.hi), index});
+    } else if (format == VGF_P2WPKH || format == VGF_P2TR || format == VGF_ETHEREUM) {
+        const char *head = format == VGF_ETHEREUM ? "0x" : format == VGF_P2TR ? "bc1p" : "bc1q";
+        const char *alphabet = format == VGF_ETHEREUM ? HEXL : BECH32;
+        const unsigned bits = format == VGF_ETHEREUM ? 4 : 5, n_data = format == VGF_ETHEREUM ? 40 : format == VGF_P2TR ? 52 : 32;
+        uint32_t st = 0;
+        for (const char *h = head; *h && !d.match_now[st]; h++) st = step(d, st, (unsigned char)*h);
+        if (d.match_now[st]) {
+            why = "matches every address";
+            return false;
+        }
+        std::vector<Prefix> prefixes;
+        if (!enumerate_prefixes(d, st, alphabet, n_data, 200000, prefixes)) {
+            why = NOT_PREFIX;
+            return false;
+        }
+        for (auto &p : prefixes)
+            if (!p.absorbing) {
+                why = NOT_PREFIX;
+                return false;
+            }
+        if (prefixes.size() > LIST_MAX_RANGES) {
+            why = "needs more than " + std::to_string(LIST_MAX_RANGES) + " payload ranges";
+            return false;
+        }
+        for (auto &p : prefixes) {
+            // a top-aligned bit prefix: the symbols' bits from the payload's most significant bit on, cut at 64
+            uint64_t v = 0;
+            unsigned pos = 0;
+            for (char c : p.s) {
+                const unsigned sym = (unsigned)(strchr(alphabet, c) - alphabet);
+                for (int k = (int)bits - 1; k >= 0; k--, pos++)
+                    if (pos < 64 && ((sym >> k) & 1)) v |= 1ull << (63 - pos);
+            }
+            const uint64_t low = pos >= 64 ? 0 : (pos == 0 ? ~0ull : (1ull << (64 - pos)) - 1);
+            if (pos == 0) {
+                why = "matches every address";
+                return false;
+            }
+            out.push_back({v, v | low, index});
+        }
+    } else {
+        why = "unknown address format";
+        return false;
+    }
+    if (out.size() == first) {
+        why = "matches no address of this format";
+        return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+DevPtab PatternList::view() const {
+    DevPtab t;
+    t.bitmap = bitmap.data();
+    t.offsets = offsets.data();
+    t.lo = lo.data();
+    t.hi = hi.data();
+    t.bits = bits;
+    t.n = (uint32_t)lo.size();
+    return t;
+}
+
+const Dfa &PatternList::dfa_of(uint32_t i, bool case_insensitive) const {
+    if (const Dfa *d = dfa[i].load(std::memory_order_acquire)) return *d;
+    std::lock_guard<std::mutex> g(mu);
+    if (const Dfa *d = dfa[i].load(std::memory_order_relaxed)) return *d;
+    Dfa *d = new Dfa();
+    std::string err;
+    (void)regex_compile(patterns[i], case_insensitive, *d, err);   // compiled once already (filter_compile_list)
+    dfa[i].store(d, std::memory_order_release);
+    return *d;
+}
+
+PatternList::~PatternList() {
+    if (dfa)
+        for (size_t i = 0; i < patterns.size(); i++) delete dfa[i].load(std::memory_order_relaxed);
+}
+
+bool filter_compile_list(const std::string &text, bool case_insensitive, uint32_t format, vgen_filter &out, std::string &err) {
+    std::shared_ptr<PatternList> L = std::make_shared<PatternList>();
+    std::vector<Range64> ranges;
+    std::unordered_map<std::string, uint32_t> seen;   // pattern -> its line
+    size_t pos = 0;
+    uint32_t line = 0;
+    while (pos < text.size()) {
+        size_t e = text.find('\n', pos);
+        if (e == std::string::npos) e = text.size();
+        std::string p = text.substr(pos, e - pos);
+        pos = e + 1;
+        line++;
+        if (!p.empty() && p.back() == '\r') p.pop_back();
+        if (p.empty() || p[0] == '#') continue;
+        const std::string at = "line " + std::to_string(line) + ": ";
+        auto dup = seen.find(p);
+        if (dup != seen.end()) {
+            err = at + "duplicate of line " + std::to_string(dup->second);
+            return false;
+        }
+        if (L->patterns.size() >= LIST_MAX_PATTERNS) {
+            err = at + "more than " + std::to_string(LIST_MAX_PATTERNS) + " patterns";
+            return false;
+        }
+        std::string why;
+        if (!list_ranges(p, case_insensitive, format, (uint32_t)L->patterns.size(), ranges, why)) {
+            err = at + "'" + p + "' " + why;
+            return false;
+        }
+        seen.emplace(p, line);
+        L->patterns.push_back(p);
+    }
+    if (L->patterns.empty()) {
+        err = "the pattern list is empty";
+        return false;
+    }
+    // disjoint intervals: sweep the range boundaries; between two boundaries the set of covering patterns is constant
+    struct Ev {
+        uint64_t at;    // first value of the piece the event opens / closes before
+        bool open;
+        bool past_end;  // a close at 2^64 (hi = 2^64 - 1)
+        uint32_t pat;
+    };
+    std::vector<Ev> ev;
+    ev.reserve(ranges.size() * 2);
+    for (auto &r : ranges) {
+        ev.push_back({r.lo, true, false, r.pat});
+        ev.push_back({r.hi + 1, false, r.hi == ~0ull, r.pat});
+    }
+    std::sort(ev.begin(), ev.end(), [](const Ev &a, const Ev &b) {
+        if (a.past_end != b.past_end) return !a.past_end;
+        return a.at < b.at;
+    });
+    std::map<uint32_t, uint32_t> active;   // pattern -> ranges of it covering the current point
+    L->pat_off.push_back(0);
+    size_t k = 0;
+    while (k < ev.size()) {
+        const uint64_t at = ev[k].at;
+        const bool end = ev[k].past_end;
+        while (k < ev.size() && ev[k].at == at && ev[k].past_end == end) {
+            if (ev[k].open) active[ev[k].pat]++;
+            else if (--active[ev[k].pat] == 0) active.erase(ev[k].pat);
+            k++;
+        }
+        if (active.empty() || end) continue;
+        // the piece [at, next boundary - 1]
+        const uint64_t hi = k < ev.size() && !ev[k].past_end ? ev[k].at - 1 : ~0ull;
+        L->lo.push_back(at);
+        L->hi.push_back(hi);
+        for (auto &a : active) L->pat_idx.push_back(a.first);
+        L->pat_off.push_back((uint32_t)L->pat_idx.size());
+    }
+    // first level: about two buckets per interval, 16 .. 24 bits
+    const size_t n = L->lo.size();
+    unsigned b = 16;
+    while (b < 24 && ((size_t)1 << b) < 2 * n) b++;
+    L->bits = b;
+    const uint64_t nb = 1ull << b;
+    L->bitmap.assign((size_t)(nb / 32), 0);
+    L->offsets.assign((size_t)nb + 1, (uint32_t)n);
+    double covered = 0;
+    size_t j = 0;
+    for (uint64_t q = 0; q < nb; q++) {
+        const uint64_t first = q << (64 - b), last = first | ((1ull << (64 - b)) - 1);
+        while (j < n && L->hi[j] < first) j++;
+        L->offsets[q] = (uint32_t)j;
+        if (j < n && L->lo[j] <= last) L->bitmap[q >> 5] |= 1u << (q & 31);
+    }
+    for (size_t i = 0; i < n; i++) covered += (double)(L->hi[i] - L->lo[i]) + 1.0;
+    L->dfa.reset(new std::atomic<const Dfa *>[L->patterns.size()]);
+    for (size_t i = 0; i < L->patterns.size(); i++) L->dfa[i].store(nullptr, std::memory_order_relaxed);
+    // the list's identity: pattern texts, case flag, format
+    std::string id;
+    for (auto &p : L->patterns) {
+        id += p;
+        id.push_back('\n');
+    }
+    id += case_insensitive ? "i" : "-";
+    id += std::to_string(format);
+    host_sha256((const uint8_t *)id.data(), id.size(), L->digest);
+
+    out.pattern.clear();
+    out.case_insensitive = case_insensitive;
+    out.format = format;
+    memset(&out.dev, 0, sizeof out.dev);
+    out.dev.kind = DEVF_LIST;
+    out.selectivity = covered / 18446744073709551616.0;
+    out.list = L;
+    return true;
+}
+
+bool payload_from_address(uint32_t format, const std::string &address, uint8_t out[32]) {
+    std::string a = address;
+    if (format == VGF_P2PKH || format == VGF_P2PKH_UNCOMPRESSED || format == VGF_P2SH_P2WPKH) {
+        if (a.empty() || a.size() > 40) return false;
+        uint8_t v[25] = {0};   // the 25-byte payload integer, big-endian
+        for (char c : a) {
+            const int dg = b58_digit(c);
+            if (dg < 0) return false;
+            unsigned carry = (unsigned)dg;
+            for (int i = 24; i >= 0; i--) {
+                carry += 58u * v[i];
+                v[i] = (uint8_t)carry;
+                carry >>= 8;
+            }
+            if (carry) return false;
+        }
+        memcpy(out, v + 1, 20);
+    } else if (format == VGF_ETHEREUM) {
+        if (a.size() != 42 || a[0] != '0' || (a[1] != 'x' && a[1] != 'X')) return false;
+        for (int i = 0; i < 20; i++) {
+            int hv[2];
+            for (int h = 0; h < 2; h++) {
+                const char c = (char)tolower((unsigned char)a[2 + 2 * i + h]);
+                const char *q = c ? strchr(HEXL, c) : nullptr;
+                if (!q) return false;
+                hv[h] = (int)(q - HEXL);
+            }
+            out[i] = (uint8_t)(hv[0] << 4 | hv[1]);
+        }
+        return true;   // any casing decodes; the patterns' automata judge the string itself
+    } else if (format == VGF_P2WPKH || format == VGF_P2TR) {
+        const size_t n_data = format == VGF_P2TR ? 52 : 32, len = 4 + n_data + 6;
+        if (a.size() != len) return false;
+        for (auto &c : a) c = (char)tolower((unsigned char)c);
+        uint32_t acc = 0;
+        int bits = 0;
+        size_t o = 0;
+        for (size_t i = 4; i < 4 + n_data; i++) {
+            const char *q = a[i] ? strchr(BECH32, a[i]) : nullptr;
+            if (!q) return false;
+            acc = (acc << 5) | (uint32_t)(q - BECH32);
+            bits += 5;
+            if (bits >= 8) {
+                bits -= 8;
+                out[o++] = (uint8_t)(acc >> bits);
+            }
+        }
+        // (the re-encoding below checks the header, the padding and the checksum; a mixed-case string is no address)
+        bool lower = false, upper = false;
+        for (char c : address) {
+            lower = lower || (c >= 'a' && c <= 'z');
+            upper = upper || (c >= 'A' && c <= 'Z');
+        }
+        if (lower && upper) return false;
+    } else {
+        return false;
+    }
+    // exact: the string must be the encoding of the payload it decodes to (version byte, checksum, padding)
+    return address_from_payload(format, out) == a;
+}
+
+void filter_which(const vgen_filter &f, const std::string &address, const uint8_t *payload, std::vector<uint32_t> &out) {
+    out.clear();
+    if (!f.list) {
+        if (f.dfa.is_match(address)) out.push_back(0);
+        return;
+    }
+    uint8_t buf[32];
+    if (!payload) {
+        if (!payload_from_address(f.format, address, buf)) return;
+        payload = buf;
+    }
+    u32 w[2];
+    memcpy(w, payload, 8);
+    const PatternList &L = *f.list;
+    const int j = ptab_find(L.view(), ptab_top64(w));
+    if (j < 0) return;
+    for (uint32_t k = L.pat_off[j]; k < L.pat_off[j + 1]; k++)
+        if (L.dfa_of(L.pat_idx[k], f.case_insensitive).is_match(address)) out.push_back(L.pat_idx[k]);
+}
+
+bool filter_accepts(const vgen_filter &f, const std::string &address, const uint8_t *payload) {
+    if (!f.list) return f.dfa.is_match(address);
+    std::vector<uint32_t> w;
+    filter_which(f, address, payload, w);
+    return !w.empty();
 }
 
 }  // namespace vg

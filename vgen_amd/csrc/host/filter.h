@@ -12,11 +12,39 @@
 #pragma once
 #include <stdint.h>
 
+#include <atomic>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../device/device_types.h"
 #include "regex_dfa.h"
+
+namespace vg {
+
+// A compiled pattern list (vgen_filter_compile_list; device kind DEVF_LIST).  Every pattern is a start-anchored prefix
+// whose matches are ranges of the big-endian payload; the ranges of all patterns, cut to the top 64 bits, are split into
+// disjoint sorted intervals, each naming the patterns it can satisfy.  The device looks candidates up in the interval
+// table (core/ptab_eval.h); the host confirms each with the exact automata of its interval's patterns, built at first use.
+struct PatternList {
+    std::vector<std::string> patterns;     // pattern i = the i-th pattern line
+    std::vector<uint64_t> lo, hi;          // disjoint intervals of the top 64 payload bits, sorted
+    std::vector<uint32_t> pat_off;         // patterns of interval j: pat_idx[pat_off[j] .. pat_off[j + 1]), ascending
+    std::vector<uint32_t> pat_idx;
+    uint32_t bits = 16;                    // first level: buckets of the top `bits` bits
+    std::vector<uint32_t> bitmap, offsets; // (core/ptab_eval.h)
+    uint8_t digest[32] = {0};              // SHA-256 over the pattern texts, the case flag and the format (checkpoints)
+    // pattern i's exact automaton, compiled at first use: built under mu, published through the atomic pointer, then read
+    // without a lock (every candidate of every confirming thread looks one up)
+    mutable std::mutex mu;
+    mutable std::unique_ptr<std::atomic<const Dfa *>[]> dfa;
+    ~PatternList();
+    DevPtab view() const;                  // host pointers into the vectors above
+    const Dfa &dfa_of(uint32_t i, bool case_insensitive) const;
+};
+
+}  // namespace vg
 
 struct vgen_filter {
     std::string pattern;
@@ -27,6 +55,7 @@ struct vgen_filter {
     double selectivity = 1.0;   // estimated fraction of keys the device reports
     std::vector<uint32_t> chk_lut;   // Bech32 checksum tables (20 x 256) when the prefilter tests the checksum
     std::vector<uint32_t> dfa_blob;  // DEVF_DFA: the DFA in device layout (core/dfa_eval.h)
+    std::shared_ptr<vg::PatternList> list;   // DEVF_LIST: the pattern list (dfa above stays empty)
 };
 
 namespace vg {
@@ -34,5 +63,20 @@ namespace vg {
 // Compiles pattern + derives the device prefilter for `format`. false + err on invalid patterns.
 bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t format, vgen_filter &out,
                     std::string &err);
+
+// Hard limit on the patterns of one list (vgen_hip.h: vgen_filter_compile_list).
+constexpr uint32_t LIST_MAX_PATTERNS = 1u << 20;
+// Compiles a pattern list (one pattern per line; empty lines and lines starting with '#' skipped) for `format`.  false +
+// err ("line N: reason") when a line is not a start-anchored prefix, matches every address or none, repeats an earlier
+// line, or the list is empty.
+bool filter_compile_list(const std::string &text, bool case_insensitive, uint32_t format, vgen_filter &out, std::string &err);
+// The payload of an address of `format` (Base58Check / Bech32 / Bech32m / hex decoded and checked); false when the string
+// is not such an address.  out: 20 bytes, 32 for P2TR.
+bool payload_from_address(uint32_t format, const std::string &address, uint8_t out[32]);
+// Pattern indices the address satisfies, ascending: a list's through its interval table and the automata of the interval's
+// patterns; a single pattern's {0} or {}.  `payload` (optional) spares the decode when the caller has it.
+void filter_which(const vgen_filter &f, const std::string &address, const uint8_t *payload, std::vector<uint32_t> &out);
+// Pattern::matches for either kind of filter (a list: any of its patterns).
+bool filter_accepts(const vgen_filter &f, const std::string &address, const uint8_t *payload);
 
 }  // namespace vg

@@ -476,6 +476,8 @@ void rt_destroy(vgen_ctx *c) {
     if (c->d_dump_slab2) (void)hipFree(c->d_dump_slab2);
     if (c->h_dump_slab2) (void)hipHostFree(c->h_dump_slab2);
     if (c->d_keys_slab) (void)hipFree(c->d_keys_slab);
+    if (c->d_list_slab) (void)hipFree(c->d_list_slab);
+    if (c->d_ptab) (void)hipFree(c->d_ptab);
     if (c->d_rtab) (void)hipFree(c->d_rtab);
     if (c->d_gtab) (void)hipFree(c->d_gtab);
     release_gtab(c);                              // the wide table is shared per device: freed with its last user
@@ -565,6 +567,72 @@ int ensure_dump_frame(vgen_ctx *c, uint32_t frame) {
 }
 
 bool dump_mode(const vgen_ctx *c) { return !c->have_filter || c->h_filter.kind == DEVF_HOST_ALL; }
+bool list_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind == DEVF_LIST; }
+
+// The pattern-list buffers of every frame: the payloads of a dispatch (20 B per key, x 6 on an endomorphism context, 32 B for
+// P2TR) and the hit mask (one bit per slot).  Device memory only — the payloads never leave the device — so, unlike dump mode,
+// every frame has them.
+int ensure_list_slab(vgen_ctx *c) {
+    if (c->d_list_slab) return VGEN_OK;
+    const size_t slots = (size_t)c->batch * (c->endo ? 6 : 1);
+    const size_t pay_b = up256(slots * c->payload_words * sizeof(uint32_t)), hits_b = up256(slots / 8);
+    const size_t per = pay_b + hits_b;
+    std::string refused;
+    if (!mem_allows(c, (uint64_t)per * c->frames, false, false, &refused)) return c->fail(VGEN_E_NOMEM, "pattern-list buffers: " + refused);
+    if (hipMalloc((void **)&c->d_list_slab, per * c->frames) != hipSuccess) return c->fail(VGEN_E_NOMEM, "pattern-list buffer allocation failed");
+    c->mode_bytes += (uint64_t)per * c->frames;
+    for (uint32_t i = 0; i < c->frames; i++) {
+        c->fr[i].d_list = reinterpret_cast<uint32_t *>(c->d_list_slab + per * i);
+        c->fr[i].d_hits = reinterpret_cast<unsigned long long *>(c->d_list_slab + per * i + pay_b);
+    }
+    return VGEN_OK;
+}
+
+// Uploads a list's interval table (core/ptab_eval.h) and points c->ptab at the device copy.
+int upload_ptab(vgen_ctx *c, const PatternList &L) {
+    const size_t bm_b = up256(L.bitmap.size() * 4), off_b = up256(L.offsets.size() * 4), lo_b = up256(L.lo.size() * 8);
+    const size_t need = bm_b + off_b + 2 * lo_b;
+    if (need > c->ptab_bytes) {
+        std::string refused;
+        if (!mem_allows(c, need - c->ptab_bytes, false, false, &refused)) return c->fail(VGEN_E_NOMEM, "pattern-list table: " + refused);
+        uint8_t *d = nullptr;
+        if (hipMalloc((void **)&d, need) != hipSuccess) return c->fail(VGEN_E_NOMEM, "pattern-list table allocation failed");
+        if (c->d_ptab) (void)hipFree(c->d_ptab);
+        c->mode_bytes += need - c->ptab_bytes;
+        c->d_ptab = d;
+        c->ptab_bytes = need;
+    }
+    uint8_t *d = c->d_ptab;
+    if (int rc = upload(c, d, L.bitmap.data(), L.bitmap.size() * 4)) return rc;
+    if (int rc = upload(c, d + bm_b, L.offsets.data(), L.offsets.size() * 4)) return rc;
+    if (int rc = upload(c, d + bm_b + off_b, L.lo.data(), L.lo.size() * 8)) return rc;
+    if (int rc = upload(c, d + bm_b + off_b + lo_b, L.hi.data(), L.hi.size() * 8)) return rc;
+    c->ptab.bitmap = reinterpret_cast<const uint32_t *>(d);
+    c->ptab.offsets = reinterpret_cast<const uint32_t *>(d + bm_b);
+    c->ptab.lo = reinterpret_cast<const uint64_t *>(d + bm_b + off_b);
+    c->ptab.hi = reinterpret_cast<const uint64_t *>(d + bm_b + off_b + lo_b);
+    c->ptab.bits = L.bits;
+    c->ptab.n = (uint32_t)L.lo.size();
+    return VGEN_OK;
+}
+
+// The two list kernels behind the per-key kernels of a list dispatch on frame f (count slots written per image).
+int enqueue_ptab(vgen_ctx *c, vgen_ctx::Frame &f, uint32_t count, bool endo) {
+    PtabArgs p;
+    memset(&p, 0, sizeof p);
+    p.tab = c->ptab;
+    p.payloads = f.d_list;
+    p.hits = f.d_hits;
+    p.mhdr = reinterpret_cast<DevMatchHeader *>(f.d_match);
+    p.mrec = reinterpret_cast<DevMatch *>(f.d_match + sizeof(DevMatchHeader));
+    p.stride = c->batch;
+    p.count = count;
+    p.images = endo ? 6 : 1;
+    p.match_base = f.match_base;
+    p.match_cap = c->match_cap;
+    HIP_TRY(c, launch_ptab(p, (int)c->payload_words, f.s));
+    return VGEN_OK;
+}
 
 }  // namespace
 
@@ -577,6 +645,14 @@ int rt_set_filter(vgen_ctx *c, const vgen_filter *f) {
         return ensure_dump_slab(c);
     }
     if (f->format != c->format) return c->fail(VGEN_E_INVALID, "filter was compiled for another address format");
+    if (f->list) {   // a pattern list: its table and the frames' payload buffers (the per-key kernels run as in dump mode)
+        if (int rc = ensure_list_slab(c)) return rc;
+        if (int rc = upload_ptab(c, *f->list)) return rc;
+        c->h_filter = f->dev;
+        if (int rc = upload(c, c->d_filter, &c->h_filter, sizeof(DevFilter))) return rc;
+        c->have_filter = true;
+        return VGEN_OK;
+    }
     c->h_filter = f->dev;
     if (f->dev.chk_lut) {   // Bech32 checksum tables: upload and point the device copy at them
         if (!c->d_chk_lut) {
@@ -1136,10 +1212,13 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
     const bool endo_now = c->endo && !(a.dfa_bytes && parks_y && a.dfa_bytes + 2u * 9u * KEYS_WG * 4u > 64u * 1024u);
     a.endo = endo_now ? 1u : 0u;
     a.vstride = c->batch;
+    const bool listed = list_mode(c);
     if (dump) {
         if (int rc = ensure_dump_frame(c, (uint32_t)(&f - c->fr.data()))) return rc;
         if (n < c->batch) HIP_TRY(c, hipMemsetAsync(f.d_dump, 0, (size_t)c->batch * (endo_now ? 6 : 1) * c->payload_words * sizeof(uint32_t), f.s));
         a.dump = f.d_dump;
+    } else if (listed) {
+        a.dump = f.d_list;   // dump mode into the device-only buffer; the list kernels read the first n slots of every image
     } else {
         a.mhdr = reinterpret_cast<DevMatchHeader *>(f.d_match);
         a.mrec = reinterpret_cast<DevMatch *>(f.d_match + sizeof(DevMatchHeader));
@@ -1155,6 +1234,8 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
     HIP_TRY(c, launch_keys_scan((int)c->format, a, f.s, c->timing ? f.ev_mid : nullptr));
     if (c->format == VGF_P2TR)
         if (int rc = enqueue_p2tr_stage(c, f, a, n)) return rc;
+    if (listed)
+        if (int rc = enqueue_ptab(c, f, n, endo_now)) return rc;
     return finish_dispatch(c, f, dump, endo_now ? (uint64_t)n * 6 : n, endo_now);
 }
 
@@ -1221,9 +1302,12 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
         a.lone = others <= c->lone_max_others;
     }
     const bool dump = dump_mode(c);
+    const bool listed = list_mode(c);
     if (dump) {
         if (int rc = ensure_dump_frame(c, (uint32_t)(&f - c->fr.data()))) return rc;
         a.dump = f.d_dump;
+    } else if (listed) {
+        a.dump = f.d_list;   // dump mode into the device-only buffer, then the list kernels
     } else {
         a.mhdr = reinterpret_cast<DevMatchHeader *>(f.d_match);
         a.mrec = reinterpret_cast<DevMatch *>(f.d_match + sizeof(DevMatchHeader));
@@ -1260,6 +1344,8 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
     HIP_TRY(c, launch_seq_fwd(a, f.s));
     if (c->timing) HIP_TRY(c, hipEventRecord(f.ev_mid, f.s));
     HIP_TRY(c, launch_seq_bwd((int)c->format, a, f.s));
+    if (listed)
+        if (int rc = enqueue_ptab(c, f, c->batch, endo_now)) return rc;
     return finish_dispatch(c, f, dump, endo_now ? (uint64_t)c->batch * 6 : c->batch, endo_now);
 }
 

@@ -77,12 +77,20 @@ struct vgen_ctx {
     uint32_t *d_chk_lut = nullptr;       // Bech32 checksum tables of the current filter (when it tests the checksum)
     bool have_filter = false;            // false = dump mode
     vg::DevFilter h_filter{};
+    // DEVF_LIST: the list's interval table on the device (bitmap | offsets | lo | hi), and the frames' device-only payload
+    // buffers + hit masks (made by vgen_set_filter when a list is first set: never on the dispatch path)
+    uint8_t *d_ptab = nullptr;
+    size_t ptab_bytes = 0;               // allocated size of d_ptab
+    vg::DevPtab ptab{};                  // device pointers into d_ptab
+    uint8_t *d_list_slab = nullptr;
 
     struct Frame {
         hipStream_t s = nullptr;         // this frame's stream (owned by the context): carries the whole dispatch chain
         hipEvent_t ev_done = nullptr;    // dispatch complete incl. its copies: what vgen_wait waits on when streams share queues, no timing
         hipEvent_t ev_start = nullptr, ev_mid = nullptr, ev_stop = nullptr;   // VGEN_FLAG_TIMING: before fwd / before bwd / after bwd
         uint32_t *d_dump = nullptr;      // dump mode: slice of d_dump_slab
+        uint32_t *d_list = nullptr;      // pattern list: the dispatch's payloads (slice of d_list_slab, no host mirror) ...
+        unsigned long long *d_hits = nullptr;   // ... and the lookup's hit mask, one bit per payload slot
         uint8_t *h_dump = nullptr;       // dump mode: pinned mirror, filled by the dispatch's own async copy
         uint8_t *d_keys = nullptr;       // explicit keys of vgen_dispatch_keys (slice of d_keys_slab)
         uint32_t *d_keys_scratch = nullptr;   // arbitrary-scalar path: Jacobian results | tree | roots (slice of d_keys_slab)

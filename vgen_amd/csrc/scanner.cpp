@@ -22,6 +22,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <memory>
 #include <random>
@@ -89,6 +90,7 @@ void random_valid_key(Scalar &k) {
 // variant * batch + i and the key is variant `index / batch` of batch_start + i (host/scalar.h).
 // How a batch's candidate index maps to its private key: batch_start + index (the walk), or the counter-based stream.
 struct BatchKeys {
+    uint64_t batch_no = 0;   // this shard's batch number (checkpointed batches included)
     Scalar start{};
     bool random = false;
     RndSeed seed{};
@@ -177,7 +179,7 @@ private:
 bool make_match(const vgen_filter &flt, uint32_t format, const BatchKeys &bk, uint32_t index,
                 const uint8_t *payload, const Scalar *end, LiteMatch &g, uint32_t batch = 0, uint32_t images = 1) {
     std::string addr = address_from_payload(format, payload);
-    if (addr.empty() || addr.size() >= sizeof g.address || !flt.dfa.is_match(addr)) return false;          // pattern.matches, gpu.rs:1069
+    if (addr.empty() || addr.size() >= sizeof g.address || !filter_accepts(flt, addr, payload)) return false;   // pattern.matches, gpu.rs:1069
     Scalar k;
     const uint32_t variant = images > 1 ? index / batch : 0;
     if (images > 1) index %= batch;
@@ -220,6 +222,79 @@ bool lite_from_key(uint32_t format, const uint8_t kb[32], LiteMatch &g) {
     memcpy(g.address, addr.c_str(), addr.size() + 1);
     return true;
 }
+
+// The per-pattern bookkeeping of a pattern-list scan (vgen_scan_list).  Shards hand in the confirmed matches of every batch
+// they commit, keyed by the batch's GLOBAL number (batch * shards + shard); the ledger applies them in that order — what
+// vgen_scan's order is on one context — so that "the first per_pattern keys of the walk that satisfy pattern i" does not
+// depend on which context finished first.  A match is taken when it satisfies a pattern that still wants matches; it then
+// counts toward every pattern it satisfies.
+struct ListLedger {
+    const vgen_filter *flt = nullptr;
+    uint64_t per_pattern = 0, count = UINT64_MAX;
+    uint32_t shards = 1;
+    std::vector<uint64_t> recorded;       // per shard: batches a resumed checkpoint already holds (applied up front)
+    std::mutex mu;
+    std::vector<uint64_t> got;            // matches taken per pattern
+    uint64_t unsatisfied = 0;             // patterns below per_pattern (per_pattern > 0)
+    std::map<uint64_t, std::vector<LiteMatch>> pending;   // committed batches waiting for the ones before them
+    uint64_t next = 0;                    // global batch applied next
+    std::vector<LiteMatch> accepted;
+    std::atomic<bool> done{false};
+    std::atomic<uint64_t> n_accepted{0};
+    bool arrival = false;                 // contexts that walk from bases of their own (VGEN_FLAG_ENDO): no global order to keep
+
+    void init(const vgen_filter *f, uint64_t pp, uint64_t cnt, uint32_t n_shards) {
+        flt = f;
+        per_pattern = pp;
+        count = cnt;
+        shards = std::max(1u, n_shards);
+        got.assign(f->list->patterns.size(), 0);
+        unsatisfied = pp ? got.size() : 0;
+        recorded.assign(shards, 0);
+        done = count == 0;
+    }
+    // (under mu)
+    void apply(const std::vector<LiteMatch> &v) {
+        std::vector<uint32_t> which;
+        for (const LiteMatch &m : v) {
+            if (done) return;
+            filter_which(*flt, m.address, nullptr, which);
+            bool want = per_pattern == 0 && !which.empty();
+            for (uint32_t i : which) want = want || got[i] < per_pattern;
+            if (!want) continue;
+            for (uint32_t i : which)
+                if (++got[i] == per_pattern && per_pattern) unsatisfied--;
+            accepted.push_back(m);
+            n_accepted.store(accepted.size(), std::memory_order_relaxed);
+            if (accepted.size() >= count || (per_pattern && unsatisfied == 0)) done = true;
+        }
+    }
+    bool is_recorded(uint64_t g) const { return g / shards < recorded[g % shards]; }
+    void submit(uint64_t g, std::vector<LiteMatch> &&v) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (arrival) {
+            apply(v);
+            return;
+        }
+        pending[g] = std::move(v);
+        for (;;) {
+            auto it = pending.find(next);
+            if (it != pending.end()) {
+                apply(it->second);
+                pending.erase(it);
+            } else if (!is_recorded(next)) {
+                break;
+            }
+            next++;
+        }
+    }
+    // the scan is over: batches still waiting behind a gap (a failed context's that nobody took over) in their order
+    void flush() {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto &kv : pending) apply(kv.second);
+        pending.clear();
+    }
+};
 
 // Threads for host-side work (candidate confirmation, rendering): the cores this process may really use — affinity mask,
 // capped by a cgroup-v2 CPU quota —, not the machine's thread count (a 256-thread host with a 16-core quota ran 256 workers).
@@ -473,7 +548,7 @@ struct SlotProgress {
 int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cfg, vgen_progress_cb cb, void *user,
                const volatile int32_t *stop, std::atomic<uint64_t> *shared_found, std::atomic<uint64_t> *shared_ops,
                MatchList &matches, uint64_t &total_ops, Checkpoint *ck = nullptr, uint32_t ck_slot = 0,
-               bool *range_done = nullptr, SlotProgress *slot = nullptr, const RndSeed *scan_seed = nullptr) {
+               bool *range_done = nullptr, SlotProgress *slot = nullptr, const RndSeed *scan_seed = nullptr, ListLedger *ll = nullptr) {
     if (cfg->format != ctx->format) return ctx->fail(VGEN_E_INVALID, "scan format differs from the context's format");
     const bool random_keys = (cfg->flags & VGEN_SCAN_RANDOM_KEYS) != 0;
     if (ctx->endo && !random_keys && (cfg->has_start || cfg->has_end || cfg->seed || cfg->n_shards > 1 || cfg->checkpoint_path))
@@ -586,13 +661,24 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     uint64_t dispatched = 0;
     total_ops = 0;
     const uint64_t count = cfg->count;
-    auto found = [&]() -> uint64_t { return shared_found ? shared_found->load(std::memory_order_relaxed) : matches.size(); };
+    auto found = [&]() -> uint64_t {
+        if (ll) return ll->n_accepted.load(std::memory_order_relaxed);
+        return shared_found ? shared_found->load(std::memory_order_relaxed) : matches.size();
+    };
+    // a pattern-list scan ends when its ledger says so (every pattern has its matches, or `count`)
+    auto scan_done = [&]() -> bool { return ll ? ll->done.load(std::memory_order_relaxed) : found() >= count; };
     std::vector<LiteMatch> batch_matches;        // matches of the batch being processed (checkpoint commit unit)
+    std::vector<LiteMatch> batch_list;           // pattern lists: every confirmed match of the batch, for the ledger
     // A confirmed match: into the result while `count` is not reached; with a checkpoint ALWAYS into the batch's
     // ledger entry, so that a committed batch is recorded with all of its matches and a later run with a larger
     // count loses none.  Returns false when the match was dropped (no checkpoint, count reached).
     uint64_t taken_uncommitted = 0;   // matches taken from the batch in hand, not yet committed (rolled back if the scan fails first)
     auto push = [&](const LiteMatch &g) -> bool {
+        if (ll) {   // the ledger decides, in global batch order, when the batch is committed
+            batch_list.push_back(g);
+            if (ck) batch_matches.push_back(g);
+            return true;
+        }
         const bool take = found() < count;
         if (take) {
             matches.push_back(g);
@@ -605,6 +691,13 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     // The workers' confirmed matches of one batch (index order: part 0, part 1, ...), handed over in bulk: as many as `count`
     // still has room for, all of them into the checkpoint's batch record.  Returns true when some were dropped.
     auto push_parts = [&](std::vector<std::vector<LiteMatch>> &part) -> bool {
+        if (ll) {
+            for (auto &p : part) {
+                if (ck) batch_matches.insert(batch_matches.end(), p.begin(), p.end());
+                batch_list.insert(batch_list.end(), p.begin(), p.end());
+            }
+            return false;
+        }
         size_t total = 0;
         for (auto &p : part) total += p.size();
         const uint64_t have = found();
@@ -647,6 +740,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
             int r = vgen_dispatch_random_seed(ctx, frame, sb, shard, first);
             if (r != VGEN_OK) return r;
             pend[frame] = BatchKeys{};
+            pend[frame].batch_no = batch_no;
             pend[frame].random = true;
             pend[frame].seed = rnd_seed;
             pend[frame].stream = shard;
@@ -659,6 +753,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
         int r = vgen_dispatch(ctx, frame, kb);
         if (r != VGEN_OK) return r;
         pend[frame] = BatchKeys{};
+        pend[frame].batch_no = skipped + dispatched;
         pend[frame].start = current;
         dispatched++;
         Scalar nx;
@@ -685,7 +780,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     const bool table_path = random_keys || ctx->format == VGF_P2TR;
     const auto scan_t0 = std::chrono::steady_clock::now();
     bool upgrade_asked = false;
-    auto may_launch = [&]() { return can_dispatch() && !stopped() && found() < count; };
+    auto may_launch = [&]() { return can_dispatch() && !stopped() && !scan_done(); };
     // (a frame's stream — a hardware queue of its own — is created at its first dispatch and takes ~8 ms: a fresh context
     // starts on frame 0 alone, so that an easy pattern's first match does not wait for a second queue it never needs)
     auto prime = [&]() {
@@ -731,15 +826,15 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
             // batch is recorded with every match it holds).
             const uint32_t total = (uint32_t)tested;   // N, or 6 N for an endomorphism dispatch
             uint32_t pos = 0;
-            for (unsigned round = 0; pos < total && (ck || found() < count); round++) {
+            for (unsigned round = 0; pos < total && (ck || ll || found() < count); round++) {
                 const uint64_t have = found();
-                const uint64_t need = ck ? total : have < count ? count - have : 0;
+                const uint64_t need = ck || ll ? total : have < count ? count - have : 0;
                 uint64_t len = total - pos;
-                if (!ck && need < total / 8) len = std::min<uint64_t>(len, std::max<uint64_t>(need * 4, 64) << std::min(2 * round, 24u));
+                if (!ck && !ll && need < total / 8) len = std::min<uint64_t>(len, std::max<uint64_t>(need * 4, 64) << std::min(2 * round, 24u));
                 if (len < 1024) {
                     LiteMatch g;
                     const uint32_t stop_at = pos + (uint32_t)len;
-                    for (; pos < stop_at && (ck || found() < count); pos++)
+                    for (; pos < stop_at && (ck || ll || found() < count); pos++)
                         if (make_match(flt, cfg->format, batch_start, pos, dump + (size_t)pos * pbytes, end, g, N, images)) (void)push(g);
                     continue;
                 }
@@ -819,7 +914,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
                 prof_cand += n_found;
 #endif
             } else {
-                for (; i < n_found && (ck || found() < count); i++)
+                for (; i < n_found && (ck || ll || found() < count); i++)
                     if (make_match(flt, cfg->format, batch_start, recs[i].index, recs[i].payload, end, g, N, images)) (void)push(g);
                 cut = i < n_found;   // candidates left unexamined (conservative: they may not all be matches)
             }
@@ -830,11 +925,13 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
         // `count`: the file stays a consistent prefix of the scan whatever count a later run asks for.
         cut_any = cut_any || cut;
         if (ck) ck->commit(ck_slot, batch_matches, tested);
+        if (ll) ll->submit(batch_start.batch_no * shards + shard, std::move(batch_list));
+        batch_list.clear();
         if (slot) slot->done.fetch_add(1);
         taken_uncommitted = 0;
         batch_matches.clear();
         if (cb) cb(shared_ops ? tested : total_ops, user);   // multi-device: the wrapper adds N to the shared count under its lock
-        if (found() >= count && !dispatched_next) break;   // gpu.rs:1111
+        if (scan_done() && !dispatched_next) break;   // gpu.rs:1111
         if (table_path && !upgrade_asked && std::chrono::duration<double>(std::chrono::steady_clock::now() - scan_t0).count() >= 5.0) {
             rt_prefer_table_bits(ctx, 29, cfg->table_bits_max);   // taken into use when it is complete; nothing waits
             upgrade_asked = true;
@@ -1032,19 +1129,11 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
 // Multi-device scan: one host thread per context, batches striped over the contexts (context i takes
 // global batches b = i mod n), a shared match counter and stop flag, results merged in ascending key
 // order and truncated to `count` (no collective, host-side aggregation only).
-extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const vgen_scan_config *cfg_in,
-                               vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out) {
-    vgen_scan_config cfg_full;
-    if (!ctxs || n_ctx == 0 || !pattern || !out || !normalise_scan_config(cfg_in, cfg_full)) return VGEN_E_INVALID;
-    const vgen_scan_config *cfg = &cfg_full;
-    for (uint32_t i = 0; i < n_ctx; i++)
-        if (!ctxs[i] || ctxs[i]->batch != ctxs[0]->batch) return VGEN_E_INVALID;
-    memset(out, 0, sizeof *out);
+// The body of vgen_scan_multi for a compiled filter; `pattern` names the scan in a checkpoint.  With `ll` (vgen_scan_list)
+// the shards hand their confirmed matches to the list's ledger, which decides what the scan returns.
+static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &flt, const char *pattern, const vgen_scan_config *cfg,
+                          vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out, ListLedger *ll) {
     const auto t0 = std::chrono::steady_clock::now();
-    vgen_filter flt;
-    std::string err;
-    if (!filter_compile(pattern, cfg->case_insensitive != 0, cfg->format, flt, err))
-        return ctxs[0]->fail(VGEN_E_PATTERN, err);
     vgen_scan_config base = *cfg;
     Checkpoint ck;
     Checkpoint *ckp = nullptr;
@@ -1074,7 +1163,16 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
     }
     std::atomic<uint64_t> found{0}, ops_shared{0};
     if (ckp) found = ck.ledger.size();
-    const bool skip_all = ckp && (ck.complete || ck.ledger.size() >= cfg->count);
+    if (ll) {
+        ll->arrival = own_bases && n_ctx > 1;
+        if (ckp) {   // what earlier runs confirmed counts first, in the order it was recorded
+            std::lock_guard<std::mutex> g(ll->mu);
+            ll->recorded = ck.done;
+            ll->apply(ck.ledger);
+            while (ll->is_recorded(ll->next)) ll->next++;
+        }
+    }
+    const bool skip_all = ckp && (ck.complete || (ll ? ll->done.load() : ck.ledger.size() >= cfg->count));
     // Per SLOT of the striping (slot i starts on context i): matches, operations, progress, whether its range ran out.
     // Per CONTEXT: the status of its last scan_shard.  A context that fails retires; its slot is left where its last
     // committed batch put it, and a context that has finished its own slot takes it over from there (the reference has one
@@ -1100,7 +1198,7 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
         c->cb(c->ops->fetch_add(delta) + delta, c->user);
     };
     auto scan_over = [&]() {
-        return (stop && __atomic_load_n(const_cast<const int32_t *>(stop), __ATOMIC_RELAXED) != 0) || found.load() >= cfg->count;
+        return (stop && __atomic_load_n(const_cast<const int32_t *>(stop), __ATOMIC_RELAXED) != 0) || (ll ? ll->done.load() : found.load() >= cfg->count);
     };
     std::vector<std::thread> th;
     for (uint32_t i = 0; i < n_ctx && !skip_all; i++)
@@ -1114,7 +1212,7 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
                 MatchList got;
                 uint64_t o = 0;
                 const int rc = scan_shard(ctxs[i], flt, &c, cb ? (vgen_progress_cb)locked_cb : nullptr, &cbc, stop, &found, &ops_shared,
-                                          got, o, ckp, slot, &rd, own_bases ? nullptr : &progress[slot], random_keys ? &rnd_seed : nullptr);
+                                          got, o, ckp, slot, &rd, own_bases ? nullptr : &progress[slot], random_keys ? &rnd_seed : nullptr, ll);
                 std::unique_lock<std::mutex> lk(q_mu);
                 part[slot].append(std::move(got));
                 ops[slot] += o;
@@ -1169,15 +1267,20 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
     out->failed_shards = (int32_t)failed_ctx;
     std::vector<LiteMatch> all;
     uint64_t total = 0;
-    if (ckp) all = ck.ledger;   // earlier runs' matches + every batch committed by this one
+    if (ckp && !ll) all = ck.ledger;   // earlier runs' matches + every batch committed by this one
     for (uint32_t i = 0; i < n_ctx; i++) {
-        if (!ckp) {
+        if (!ckp && !ll) {
             const std::vector<LiteMatch> flat = part[i].flatten();
             all.insert(all.end(), flat.begin(), flat.end());
         }
         total += ops[i];
     }
-    std::sort(all.begin(), all.end(), [](const LiteMatch &a, const LiteMatch &b) { return memcmp(a.key, b.key, 32) < 0; });
+    if (ll) {   // the ledger's matches, in the scan's order
+        ll->flush();
+        all = ll->accepted;
+    } else {
+        std::sort(all.begin(), all.end(), [](const LiteMatch &a, const LiteMatch &b) { return memcmp(a.key, b.key, 32) < 0; });
+    }
     if (all.size() > cfg->count) all.resize((size_t)cfg->count);
     const std::string why = first_err != VGEN_OK ? ctxs[first_err_ctx]->err : std::string();
     const int frc = finish_result(ctxs[0], cfg->format, all, total, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
@@ -1189,6 +1292,43 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
     }
     if (first_err != VGEN_OK) ctxs[first_err_ctx]->err = why;   // absorbed: still readable through vgen_last_error(ctxs[i])
     return frc;
+}
+
+extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const vgen_scan_config *cfg_in,
+                               vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out) {
+    vgen_scan_config cfg_full;
+    if (!ctxs || n_ctx == 0 || !pattern || !out || !normalise_scan_config(cfg_in, cfg_full)) return VGEN_E_INVALID;
+    const vgen_scan_config *cfg = &cfg_full;
+    for (uint32_t i = 0; i < n_ctx; i++)
+        if (!ctxs[i] || ctxs[i]->batch != ctxs[0]->batch) return VGEN_E_INVALID;
+    memset(out, 0, sizeof *out);
+    vgen_filter flt;
+    std::string err;
+    if (!filter_compile(pattern, cfg->case_insensitive != 0, cfg->format, flt, err))
+        return ctxs[0]->fail(VGEN_E_PATTERN, err);
+    return scan_multi_run(ctxs, n_ctx, flt, pattern, cfg, cb, user, stop, out, nullptr);
+}
+
+// A pattern list over one or several contexts: vgen_scan_multi's loop (one context: vgen_scan's) with the list as the filter
+// and its ledger deciding which confirmed keys are results.  The checkpoint names the scan by the list's digest.
+extern "C" int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter *list, uint64_t per_pattern,
+                              const vgen_scan_config *cfg_in, vgen_progress_cb cb, void *user, const volatile int32_t *stop,
+                              vgen_scan_result *out) {
+    vgen_scan_config cfg_full;
+    if (!ctxs || n_ctx == 0 || !list || !out || !normalise_scan_config(cfg_in, cfg_full)) return VGEN_E_INVALID;
+    for (uint32_t i = 0; i < n_ctx; i++)
+        if (!ctxs[i] || ctxs[i]->batch != ctxs[0]->batch) return VGEN_E_INVALID;
+    memset(out, 0, sizeof *out);
+    if (!list->list) return ctxs[0]->fail(VGEN_E_INVALID, "vgen_scan_list needs a pattern list (vgen_filter_compile_list)");
+    if (cfg_full.format != list->format) return ctxs[0]->fail(VGEN_E_INVALID, "scan format differs from the pattern list's format");
+    cfg_full.case_insensitive = list->case_insensitive ? 1 : 0;   // the list carries it
+    cfg_full.n_shards = 0;
+    cfg_full.shard = 0;
+    const std::string id = "pattern-list:" + hex_lower(list->list->digest, 32);
+    const bool own_bases = ctxs[0]->endo && !(cfg_full.flags & VGEN_SCAN_RANDOM_KEYS);
+    ListLedger ll;
+    ll.init(list, per_pattern, cfg_full.count, own_bases ? 1 : n_ctx);
+    return scan_multi_run(ctxs, n_ctx, *list, id.c_str(), &cfg_full, cb, user, stop, out, &ll);
 }
 
 extern "C" void vgen_scan_result_free(vgen_scan_result *r) {
