@@ -52,7 +52,11 @@ typedef enum vgen_format {
     VGEN_FMT_P2SH_P2WPKH = 2,
     VGEN_FMT_P2TR = 3,
     VGEN_FMT_P2PKH_UNCOMPRESSED = 4,
-    VGEN_FMT_ETHEREUM = 5
+    VGEN_FMT_ETHEREUM = 5,
+    VGEN_FMT_ETHEREUM_CONTRACT = 6   /* not a format of the reference: the address of the contract the key's account creates with its FIRST
+                                        transaction (CREATE, nonce 0): C = keccak256(0xd6 0x94 || A || 0x80)[12..32] with A the Ethereum
+                                        address of the key.  Payload, address string and key rendering as for VGEN_FMT_ETHEREUM; the key
+                                        controls the deployer A, not C.  Other nonces: vgen_contract_address. */
 } vgen_format;
 
 /* Parameters of vgen_create; replaces the arguments of GpuRunner::new(batch_size, backend)
@@ -341,6 +345,10 @@ int vgen_key_variant(const uint8_t key_be[32], uint32_t variant, uint8_t out_be[
 /* AddressGenerator::generate (src/address.rs:92-151) on the host, for single keys (verify-style
  * use and tests). address cap >= 96, wif cap >= 72. VGEN_E_RANGE for an invalid key. */
 int vgen_derive(uint32_t format, const uint8_t key_be[32], char *address, size_t acap, char *wif, size_t wcap);
+/* Address of the contract the account `deployer` creates with the transaction of the given nonce (CREATE):
+ * keccak256(rlp([deployer, nonce]))[12..32], the nonce in its full RLP form (0 -> 0x80, 1..0x7f -> the byte itself, larger ->
+ * 0x80 + length and the big-endian bytes).  nonce 0 is what VGEN_FMT_ETHEREUM_CONTRACT searches on the device. */
+int vgen_contract_address(const uint8_t deployer[20], uint64_t nonce, uint8_t out[20]);
 
 /* ---- provider patterns (src/provider.rs) -------------------------------------------------------------- */
 

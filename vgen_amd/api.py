@@ -48,6 +48,7 @@ class AddressFormat(enum.IntEnum):
     P2tr = 3
     P2pkhUncompressed = 4
     Ethereum = 5
+    EthereumContract = 6   # VGEN_FMT_ETHEREUM_CONTRACT: the contract the key's account creates with nonce 0 (not in the reference)
 
     def charset_name(self) -> str:
         """AddressFormat::charset_name (src/address.rs:39-45)."""
@@ -143,6 +144,7 @@ _L.vgen_key_variant.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_
 _L.vgen_key_add.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
 _L.vgen_derive.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
                            ctypes.c_size_t]
+_L.vgen_contract_address.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
 _L.vgen_device_name.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
 _L.vgen_scan.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p,
                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_ScanResult)]
@@ -228,6 +230,18 @@ def key_variant(key, variant):
     out = ctypes.create_string_buffer(32)
     _check(_L.vgen_key_variant(_key(key), variant, out))
     return int.from_bytes(out.raw, "big")
+
+
+def contract_address(deployer, nonce=0) -> bytes:
+    """vgen_contract_address: the 20 bytes of the contract the account `deployer` (20 bytes, or a 0x-hex string) creates with the
+    transaction of the given nonce: keccak256(rlp([deployer, nonce]))[12:]."""
+    if isinstance(deployer, str):
+        deployer = bytes.fromhex(deployer[2:] if deployer[:2] in ("0x", "0X") else deployer)
+    if len(deployer) != 20 or not 0 <= nonce < 1 << 64:
+        raise ValueError("deployer is 20 bytes, nonce < 2^64")
+    out = ctypes.create_string_buffer(20)
+    _check(_L.vgen_contract_address(bytes(deployer), nonce, out))
+    return out.raw
 
 
 @dataclass

@@ -342,4 +342,28 @@ int vgen_derive(uint32_t format, const uint8_t key_be[32], char *address, size_t
     return VGEN_OK;
 }
 
+int vgen_contract_address(const uint8_t deployer[20], uint64_t nonce, uint8_t out[20]) {
+    if (!deployer || !out) return VGEN_E_INVALID;
+    // rlp([deployer, nonce]): list header, 0x94 + the 20 address bytes, the nonce as a big-endian integer without leading zeros
+    uint8_t msg[1 + 21 + 9], h[32];
+    size_t n = 1;
+    msg[n++] = 0x94;
+    memcpy(msg + n, deployer, 20);
+    n += 20;
+    if (nonce == 0) {
+        msg[n++] = 0x80;
+    } else if (nonce < 0x80) {
+        msg[n++] = (uint8_t)nonce;
+    } else {
+        int len = 0;
+        for (uint64_t v = nonce; v; v >>= 8) len++;
+        msg[n++] = (uint8_t)(0x80 + len);
+        for (int i = len - 1; i >= 0; i--) msg[n++] = (uint8_t)(nonce >> (8 * i));
+    }
+    msg[0] = (uint8_t)(0xc0 + (n - 1));   // payload of at most 30 bytes: short list
+    vg::host_keccak256(msg, n, h);
+    memcpy(out, h + 12, 20);
+    return VGEN_OK;
+}
+
 }  // extern "C"

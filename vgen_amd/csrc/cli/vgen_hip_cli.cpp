@@ -57,8 +57,9 @@ int format_id(const std::string &f) {
     if (f == "p2sh-p2wpkh" || f == "p2sh-p2-wpkh" || f == "p2shp2wpkh") return VGEN_FMT_P2SH_P2WPKH;
     if (f == "p2tr") return VGEN_FMT_P2TR;
     if (f == "ethereum") return VGEN_FMT_ETHEREUM;
+    if (f == "ethereum-contract") return VGEN_FMT_ETHEREUM_CONTRACT;
     if (f == "p2pkh-uncompressed") return VGEN_FMT_P2PKH_UNCOMPRESSED;
-    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum)");
+    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract)");
 }
 
 const char *format_display(int id) {   // Display for AddressFormat, src/address.rs:48-58
@@ -68,6 +69,7 @@ const char *format_display(int id) {   // Display for AddressFormat, src/address
     case VGEN_FMT_P2WPKH: return "P2WPKH";
     case VGEN_FMT_P2SH_P2WPKH: return "P2SH-P2WPKH";
     case VGEN_FMT_P2TR: return "P2TR";
+    case VGEN_FMT_ETHEREUM_CONTRACT: return "Ethereum contract (nonce 0)";   // (no comma: the csv writer keeps eight plain columns)
     default: return "Ethereum";
     }
 }
@@ -183,6 +185,8 @@ bool parse_wif(const std::string &s, uint8_t key[32], bool *compressed) {
 void usage() {
     fprintf(stderr,
             "vgen-hip — MI355X scan engine for the vgen hot path\n\n"
+            "  FORMAT: p2pkh (default), p2wpkh, p2sh-p2wpkh, p2tr, p2pkh-uncompressed, ethereum, ethereum-contract (the address of the\n"
+            "          contract the key's account creates with its FIRST transaction, nonce 0; results carry that account as `deployer`)\n"
             "  vgen-hip generate -p PATTERN [-f FORMAT] [-i] [-c COUNT] [-o text|json|jsonl|csv|minimal] [--file PATH]\n"
             "                    [--gpu-batch-size N] [--repeat N] [-q] [--seed S] [--devices 0,1,..|all] [--frames F]\n"
             "                    [--frames F]          (dispatches in flight, default 12; several searches on ONE device share it\n"
@@ -349,7 +353,7 @@ Resolved resolve_provider(Opts &o, bool for_range) {
     vgen_provider_build_pattern(addr, o.prefix_length > 0 ? (uint32_t)o.prefix_length : 0, pat, sizeof pat);
     if (o.prefix_length > 0 || !for_range) fprintf(stderr, "Provider: %s → %s → pattern '%s'\n", o.pattern.c_str(), addr, pat);
     else fprintf(stderr, "Provider: %s → %s → exact match\n", o.pattern.c_str(), addr);
-    static const char *names[] = {"p2pkh", "p2wpkh", "p2sh-p2wpkh", "p2tr", "p2pkh-uncompressed", "ethereum"};
+    static const char *names[] = {"p2pkh", "p2wpkh", "p2sh-p2wpkh", "p2tr", "p2pkh-uncompressed", "ethereum", "ethereum-contract"};
     o.format = names[fmt];
     r.pattern = pat;
     r.from_provider = true;
@@ -574,10 +578,15 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
     for (size_t idx = 0; idx < all.size(); idx++) {
         const vgen_generated &g = all[idx];
         const std::string pattern = list ? list_pattern_of(list, g.address) : pattern_arg;
+        // ethereum-contract: the address found is the contract's; the key controls the account that has to deploy it
+        char deployer[128] = "";
+        if (fmt == VGEN_FMT_ETHEREUM_CONTRACT && vgen_derive(VGEN_FMT_ETHEREUM, g.key, deployer, sizeof deployer, nullptr, 0) != VGEN_OK)
+            die("malformed or out-of-range secret key");
         if (o.output == "text") {
             fprintf(w, "=== Match %zu of %zu ===\n", idx + 1, all.size());
             fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nWIF     : %s\nHex     : %s\n", pattern.c_str(),
                     fmt_name.c_str(), g.address, g.wif, g.hex);
+            if (deployer[0]) fprintf(w, "Deployer: %s  (the account of this key; its first transaction must create the contract)\n", deployer);
             if (!o.quiet) {
                 fprintf(w, "Ops     : %s (%.0f/sec)\n", with_commas(total_ops).c_str(), rate);
                 fprintf(w, "Time    : %s\n", format_duration(total_secs).c_str());
@@ -586,9 +595,11 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         } else if (o.output == "json" || o.output == "jsonl") {
             const bool pretty = o.output == "json";
             const char *nl = pretty ? "\n  " : "", *sp = pretty ? " " : "";
-            fprintf(w, "{%s\"address\":%s%s,%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
+            fprintf(w, "{%s\"address\":%s%s,", nl, sp, json_str(g.address).c_str());
+            if (deployer[0]) fprintf(w, "%s\"deployer\":%s%s,", nl, sp, json_str(deployer).c_str());
+            fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
                        "\"operations\":%s%llu,%s\"elapsed_secs\":%s%s,%s\"rate\":%s%s%s}\n",
-                    nl, sp, json_str(g.address).c_str(), nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str(), nl,
+                    nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str(), nl,
                     sp, json_str(fmt_name).c_str(), nl, sp, json_str(pattern).c_str(), nl, sp,
                     (unsigned long long)total_ops, nl, sp, json_f64(total_secs).c_str(), nl, sp, json_f64(rate).c_str(),
                     pretty ? "\n" : "");

@@ -197,7 +197,8 @@ VG_HD bool dfa_match_hex40(const u32 *blob, const u32 H[5]) {
     return dfa_accept(v, s);
 }
 
-// payload: NW words in memory order (5, or 8 for P2TR).  fmt: VGF_* (run time).  KFMT: what the caller knows about fmt at
+// payload: NW words in memory order (5, or 8 for P2TR).  fmt: VGF_* of the ADDRESS STRING (run time; vgf_string_format: a contract
+// address is an Ethereum address string).  KFMT: what the caller knows about fmt at
 // compile time — -1 nothing; a kernel instantiated for one payload kind passes its own format, so that it carries only the
 // encoders it can need (VGF_P2PKH: hash160 of the compressed key, i.e. P2PKH or P2WPKH, told apart by fmt; every other value: exactly that format).
 template <int NW, int KFMT = -1>
@@ -217,7 +218,7 @@ VG_HD bool dfa_match_payload_n(const u32 *blob, int fmt, const u32 *payload) {
 }
 
 VG_HD bool dfa_match_payload(const u32 *blob, int fmt, const u32 payload[5]) {
-    return dfa_match_payload_n<5>(blob, fmt, payload);
+    return dfa_match_payload_n<5>(blob, vgf_string_format(fmt), payload);
 }
 
 }  // namespace vg

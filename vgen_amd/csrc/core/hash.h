@@ -397,4 +397,27 @@ VG_HD void keccak256_pub64_addr(const u32 xw[8], const u32 yw[8], u32 out[5]) {
     out[4] = (u32)(a[3] >> 32);
 }
 
+// Address of the contract the account `acc` creates with its first transaction (CREATE, nonce 0): the low 20 bytes of
+// Keccak-256(0xd6 0x94 || acc || 0x80), the RLP encoding of the list [acc, 0] - 23 bytes, one rate block.  acc and out are five
+// words in memory order as keccak256_pub64_addr writes them, so the message words are acc's stream shifted by 16 bits.
+VG_HD void keccak256_create_addr(const u32 acc[5], u32 out[5]) {
+    u64 a[25];
+    const u32 m0 = 0x94d6u | (acc[0] << 16);
+    const u32 m1 = (acc[0] >> 16) | (acc[1] << 16), m2 = (acc[1] >> 16) | (acc[2] << 16);
+    const u32 m3 = (acc[2] >> 16) | (acc[3] << 16), m4 = (acc[3] >> 16) | (acc[4] << 16);
+    const u32 m5 = (acc[4] >> 16) | 0x01800000u;   // 0x80 = RLP of nonce 0, 0x01 = Keccak (pre-SHA-3) domain padding at byte 23
+    a[0] = (u64)m0 | ((u64)m1 << 32);
+    a[1] = (u64)m2 | ((u64)m3 << 32);
+    a[2] = (u64)m4 | ((u64)m5 << 32);
+#pragma unroll
+    for (int i = 3; i < 25; i++) a[i] = 0;
+    a[16] = 0x8000000000000000ULL;   // last byte of the 136-byte rate block
+    keccak_f1600(a);
+    out[0] = (u32)(a[1] >> 32);
+    out[1] = (u32)a[2];
+    out[2] = (u32)(a[2] >> 32);
+    out[3] = (u32)a[3];
+    out[4] = (u32)(a[3] >> 32);
+}
+
 }  // namespace vg

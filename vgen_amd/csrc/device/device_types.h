@@ -11,8 +11,14 @@ enum : int {
     VGF_P2SH_P2WPKH = 2,
     VGF_P2TR = 3,
     VGF_P2PKH_UNCOMPRESSED = 4,
-    VGF_ETHEREUM = 5
+    VGF_ETHEREUM = 5,
+    VGF_ETHEREUM_CONTRACT = 6   // address of the contract the account deploys with nonce 0 (not a format of the reference)
 };
+
+// the two formats whose payload is (derived from) the Ethereum account address: hex strings, both coordinates hashed
+constexpr bool vgf_is_eth(int fmt) { return fmt == VGF_ETHEREUM || fmt == VGF_ETHEREUM_CONTRACT; }
+// the format whose address STRING a payload of `fmt` is written as: a contract's 20 bytes are spelled like an account's
+constexpr int vgf_string_format(int fmt) { return fmt == VGF_ETHEREUM_CONTRACT ? (int)VGF_ETHEREUM : fmt; }
 
 
 // Device-side prefilter program (built by host/filter.cpp from the pattern's DFA).
@@ -95,6 +101,12 @@ struct PtabArgs {
     uint32_t images;             // 6 on an endomorphism dispatch, else 1
     uint32_t match_base;
     uint32_t match_cap;
+    // (appended: the list kernels' view of the fields above is unchanged)  payload_filter_kernel, instead of a list's table: the
+    // context's filter (device copy; nullptr = a list dispatch), the automaton of a DEVF_DFA filter and the address-string format
+    const DevFilter *filter;
+    const uint32_t *dfa_blob;
+    uint32_t dfa_bytes;
+    uint32_t fmt;
 };
 
 // Per-dispatch uniform points of the sequential kernel: Q_j = (k0 + N/2 - S/2 + j)*G and the

@@ -362,14 +362,32 @@ def prog_keccak_addr(grouped=False):
     return p, "const u32 xw[8], const u32 yw[8]", prologue
 
 
+def prog_keccak_create(grouped=False):
+    """Address of the contract an account deploys with nonce 0: the low 20 bytes of Keccak-256(0xd6 0x94 || A || 0x80), the RLP
+    list [A, 0] (core/hash.h keccak256_create_addr).  a = the account's five words as keccak_addr_block leaves them (memory order),
+    so the 23-byte message is their stream shifted by 16 bits: inputs m0..m5 = lanes 0-2, 0x01 of the padding at byte 23."""
+    p = Program(grouped)
+    lanes = [(p.input(f"m{2 * i}"), p.input(f"m{2 * i + 1}")) for i in range(3)] + [(0, 0)] * 22
+    lanes[16] = (0, 0x80000000)
+    a = p.keccak_f1600(lanes)
+    p.outputs = [a[1][1], a[2][0], a[2][1], a[3][0], a[3][1]]
+    p.prune()
+    prologue = ["u32 m0 = 0x94d6u | (a[0] << 16);"]
+    prologue += [f"u32 m{i} = (a[{i - 1}] >> 16) | (a[{i}] << 16);" for i in range(1, 5)]
+    prologue += ["u32 m5 = (a[4] >> 16) | 0x01800000u;"]
+    return p, "const u32 a[5]", prologue
+
+
 # keccak_addr_block: in round 4, in dependency order, the block ran no faster than hipcc's rolled rounds (same 5 003 instructions per key); as runs by
 # issue class with the priority changes it is worth +28 % on every Ethereum configuration (profiles/r05_keccak_ab.txt): 1 351 half-rate funnel
 # shifts against 2 844 full-rate booleans, which now ride in the second places of the issue slots.
 PROGRAMS = {"hash160_pub33_block": prog_pub33_h160, "hash160_script22_block": prog_script22_h160,
             "hash160_pub65_block": prog_pub65_h160, "base58_check_block": prog_base58_check, "keccak_addr_block": prog_keccak_addr}
 OPTIONAL = {}    # (--with NAME: blocks generated for an A/B only)
+# the second Keccak block of VGF_ETHEREUM_CONTRACT; a table of its own, emitted after PROGRAMS
+PROGRAMS_CONTRACT = {"keccak_create_block": prog_keccak_create}
 # yields per function where they differ from the default
-YIELDS = {"keccak_addr_block": "none"}
+YIELDS = {"keccak_addr_block": "none", "keccak_create_block": "none"}
 
 
 # ---- the Python model of the instruction list (CPU tests) ---------------------------------------------------------------------
@@ -643,7 +661,7 @@ def add_filler(lines, mode, n):
 
 
 def function_source(name, grouped=False, yields="every:3", window=0, distance=1, prio=None, class_window=0):
-    p, params, prologue = {**PROGRAMS, **OPTIONAL}[name](grouped)
+    p, params, prologue = {**PROGRAMS, **OPTIONAL, **PROGRAMS_CONTRACT}[name](grouped)
     left = spread(p, window, distance) if window else None
     runs = by_class(p, class_window, CLASS_DISTANCE) if class_window else None
     reg, nreg = allocate(p)
@@ -697,7 +715,7 @@ def generate(grouped=False, yields=DEFAULT_YIELD, window=0, distance=1, override
              prio=tuple(int(x) for x in DEFAULT_PRIO.split(":")), class_window=DEFAULT_CLASS_WINDOW):
     src = "// GENERATED by device/hashgen.py (`make -C vgen_amd/csrc hashblocks`) - do not edit.\n"
     src += "// The address hashes of the scan kernels as single asm statements of gfx950 instructions; see hashgen.py.\n\n"
-    for name in list(PROGRAMS) + list(extra):
+    for name in list(PROGRAMS) + list(extra) + list(PROGRAMS_CONTRACT):
         src += function_source(name, grouped, (overrides or {}).get(name, YIELDS.get(name, yields)), window, distance, prio, class_window)
     return src
 

@@ -141,7 +141,15 @@ __device__ __forceinline__ u32 match_slot(DevMatchHeader *hdr, bool hit, u32 mat
 // (7.61 against 7.75 Gkeys/s, twice; another register allocation of the Keccak rounds), so that format keeps the run-time choice.
 template <int FMT>
 struct MatchFmt {
-    static constexpr int value = (FMT == VGF_P2TR || FMT == VGF_ETHEREUM) ? -1 : FMT;
+    static constexpr int value = (FMT == VGF_P2TR || vgf_is_eth(FMT)) ? -1 : FMT;
+};
+
+// The Ethereum-contract kernels only ever write payloads (dump mode, or into the frame's device-only buffer): their filter runs
+// behind them, over the written payloads (payload_filter_kernel below), and ptab_compact_kernel makes the records - so the older
+// kernels stay the only ones that carry the match path, and the long two-block kernel has no filter registers to hold.
+template <int FMT>
+struct DumpOnly {
+    static constexpr bool value = FMT == VGF_ETHEREUM_CONTRACT;
 };
 
 template <int FMT>
@@ -174,7 +182,7 @@ __device__ __forceinline__ bool payload_from_point(const fe &x, const fe &y_cano
         u32 yw[8];
         fe_to_words(y_canon, yw);
         hash160_pub65_block(xw, yw, out);
-    } else {  // VGF_ETHEREUM
+    } else {  // VGF_ETHEREUM, VGF_ETHEREUM_CONTRACT
         u32 yw[8];
         fe_to_words(y_canon, yw);
 #if VG_KECCAK_BLOCK   // Keccak-f as one generated block of 4 195 instructions in runs by issue class (device/hashgen.py): +28 % on every Ethereum
@@ -183,6 +191,18 @@ __device__ __forceinline__ bool payload_from_point(const fe &x, const fe &y_cano
 #else
         keccak256_pub64_addr(xw, yw, out);
 #endif
+        if (FMT == VGF_ETHEREUM_CONTRACT) {
+            // the contract the account creates with nonce 0: a second rate block over 0xd6 0x94 || account || 0x80, chained from the first one's
+            // output words by 16-bit funnel shifts (hashgen.py prog_keccak_create); the blocks run one after the other, so the register peak is one block's
+            u32 acc[5];
+#pragma unroll
+            for (int i = 0; i < 5; i++) acc[i] = out[i];
+#if VG_KECCAK_BLOCK
+            keccak_create_block(acc, out);
+#else
+            keccak256_create_addr(acc, out);
+#endif
+        }
     }
     return true;
 }
@@ -310,7 +330,7 @@ __global__ void __launch_bounds__(64) seq_inv_kernel(u32 *root, u32 groups) {
 template <int FMT, bool FULL, bool ENDO = false>
 struct SeqWaves {
     // (Ethereum: four waves since the Keccak block and the running inverse in LDS; the six-image on-device matcher would spill there: three)
-    static constexpr int value = FMT == VGF_P2TR ? VG_SEQ_WAVES_P2TR : FMT == VGF_ETHEREUM ? (FULL && ENDO ? 3 : VG_SEQ_WAVES_ETH)
+    static constexpr int value = FMT == VGF_P2TR ? VG_SEQ_WAVES_P2TR : vgf_is_eth(FMT) ? (FULL && ENDO ? 3 : VG_SEQ_WAVES_ETH)
                                  : FULL ? VG_SEQ_WAVES_FULL20 : FMT == VGF_P2SH_P2WPKH ? VG_SEQ_WAVES_P2SH
                                  : FMT == VGF_P2PKH_UNCOMPRESSED ? VG_SEQ_WAVES_UNCOMP : VG_SEQ_WAVES_P2PKH;
 };
@@ -343,7 +363,7 @@ seq_bwd_kernel(const SeqArgs args) {
 #endif
     static_assert(!SPLIT || (!FULL && !ENDO && !LONE && FMT == VGF_P2PKH), "the split form parks compressed keys: x and the parity of y");
     __shared__ u32 tree[9 * WG];
-    __shared__ u32 ypark[ENDO && (FMT == VGF_P2PKH_UNCOMPRESSED || FMT == VGF_ETHEREUM) ? 9 * WG : 1];   // ENDO: the point's y
+    __shared__ u32 ypark[ENDO && (FMT == VGF_P2PKH_UNCOMPRESSED || vgf_is_eth(FMT)) ? 9 * WG : 1];   // ENDO: the point's y
     extern __shared__ u32 dyn_lds[];   // FULL: the DFA blob
     constexpr int NW = PayloadWords<FMT>::value;
     // PARK: the lane's table point R_u and the running inverse live in LDS between their uses instead of in 27 registers (LDS reads
@@ -354,7 +374,7 @@ seq_bwd_kernel(const SeqArgs args) {
     constexpr bool PARK = PARKM == 1, PARK2 = PARKM == 2;
     // PARKI: the instantiations that would otherwise spill a few registers at their 128-register cap (the uncompressed-key format: a second
     // SHA-256 block's sixteen message words; the six-image on-device matcher) keep the running inverse in 9 KB of LDS of its own instead
-    constexpr bool PARKI = VG_PARKI && !PARK && !PARK2 && !LONE && (FMT == VGF_P2PKH_UNCOMPRESSED || FMT == VGF_ETHEREUM || (FMT == VGF_P2PKH && FULL && ENDO));
+    constexpr bool PARKI = VG_PARKI && !PARK && !PARK2 && !LONE && (FMT == VGF_P2PKH_UNCOMPRESSED || vgf_is_eth(FMT) || (FMT == VGF_P2PKH && FULL && ENDO));
     __shared__ u32 rpark[PARK ? 17 * WG : (PARK2 || PARKI) ? 9 * WG : 1];   // (PARK: R.y's top limb stays in a register: 26 KB of LDS per workgroup lets six share a CU)
     const int tid = threadIdx.x;
     const GenTables gtab{args.gtab, args.gtab16, args.gtab_bits};   // P2TR: fixed-window generator tables, read from global memory (L2 / Infinity Cache / HBM)
@@ -426,7 +446,7 @@ seq_bwd_kernel(const SeqArgs args) {
     }
 
     const u32 half = args.n >> 1;
-    const bool dump = args.dump != nullptr;
+    const bool dump = DumpOnly<FMT>::value || args.dump != nullptr;
     fe zrun;            // P2TR: running product of this lane's Z(Q)
     u32 step = 0;       // P2TR: key step 0 .. 2S-1 in loop order
 
@@ -558,7 +578,7 @@ seq_bwd_kernel(const SeqArgs args) {
             if (ENDO) {
                 // compressed-key formats need only the parity of y (flipped for the negations); the others the canonical
                 // y itself, parked beside x, and p - y for the negations
-                constexpr bool NEEDS_Y = FMT == VGF_P2PKH_UNCOMPRESSED || FMT == VGF_ETHEREUM;
+                constexpr bool NEEDS_Y = FMT == VGF_P2PKH_UNCOMPRESSED || vgf_is_eth(FMT);
                 const u32 ypar = y3.n[0] & 1u;
                 lds_park_fe(tree, WG, tid, x3);
                 if (NEEDS_Y) lds_park_fe(ypark, WG, tid, y3);
@@ -1149,7 +1169,7 @@ __global__ void __launch_bounds__(KEYS_WG) keys_bwd_kernel(const KeysArgs args) 
     __builtin_amdgcn_s_setprio(VG_BASE_PRIO);   // (the level the hash blocks return to; see VG_BASE_PRIO)
 #endif
     __shared__ u32 tree[9 * KEYS_WG];
-    __shared__ u32 ypark[ENDO && (FMT == VGF_P2PKH_UNCOMPRESSED || FMT == VGF_ETHEREUM) ? 9 * KEYS_WG : 1];   // ENDO: the point's y
+    __shared__ u32 ypark[ENDO && (FMT == VGF_P2PKH_UNCOMPRESSED || vgf_is_eth(FMT)) ? 9 * KEYS_WG : 1];   // ENDO: the point's y
     extern __shared__ u32 dfa_lds[];    // FULL: the DFA blob
     constexpr int NW = PayloadWords<FMT>::value;
     const int tid = threadIdx.x;
@@ -1218,7 +1238,7 @@ __global__ void __launch_bounds__(KEYS_WG) keys_bwd_kernel(const KeysArgs args) 
     if (ENDO) {
         // (every lane has read its pair's inverse from the tree before the multiplications above; after this barrier the tree's
         //  LDS parks the x of the point in hand, as in seq_bwd_kernel)
-        constexpr bool NEEDS_Y = FMT == VGF_P2PKH_UNCOMPRESSED || FMT == VGF_ETHEREUM;
+        constexpr bool NEEDS_Y = FMT == VGF_P2PKH_UNCOMPRESSED || vgf_is_eth(FMT);
         __syncthreads();
         const u32 ypar = y.n[0] & 1u;
         lds_park_fe(tree, KEYS_WG, tid, x);
@@ -1251,7 +1271,7 @@ __global__ void __launch_bounds__(KEYS_WG) keys_bwd_kernel(const KeysArgs args) 
             (void)payload_from_point<FMT == VGF_P2TR ? VGF_P2PKH : FMT>(xe, ye, ple);
             if (idx >= args.n) continue;
             const u32 vindex = (sneg * 3u + e) * args.vstride + idx;
-            if (args.dump) {
+            if (DumpOnly<FMT>::value || args.dump) {
                 u32 *o = args.dump + (size_t)vindex * NW;
 #pragma unroll
                 for (int i = 0; i < NW; i++) o[i] = live ? ple[i] : 0u;
@@ -1273,7 +1293,7 @@ __global__ void __launch_bounds__(KEYS_WG) keys_bwd_kernel(const KeysArgs args) 
     const bool ok = payload_from_point<FMT == VGF_P2TR ? VGF_P2PKH : FMT>(x, y, pl) && valid;
 
     if (idx >= args.n) return;
-    if (args.dump) {
+    if (DumpOnly<FMT>::value || args.dump) {
         u32 *o = args.dump + (size_t)idx * NW;
 #pragma unroll
         for (int i = 0; i < NW; i++) o[i] = ok ? pl[i] : 0u;
@@ -1308,12 +1328,20 @@ static hipError_t launch_keys_fmt(const KeysArgs &a, hipStream_t stream, hipEven
         hipLaunchKernelGGL((keys_bwd_kernel<FMT, false>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
         return hipGetLastError();   // (runtime.cpp follows with launch_p2tr_tweak over the frame's taproot scratch)
     }
+    if constexpr (DumpOnly<FMT>::value) {   // payloads only: the caller filters them afterwards (launch_payload_filter)
+        constexpr int D = FMT;
+        if (!a.dump) return hipErrorInvalidValue;
+        if (a.endo) hipLaunchKernelGGL((keys_bwd_kernel<D, false, true>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+        else hipLaunchKernelGGL((keys_bwd_kernel<D, false>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+        return hipGetLastError();
+    } else {
     constexpr int F = FMT == VGF_P2TR ? VGF_P2PKH : FMT;   // (P2TR returned above: keeps its ENDO instantiations out of the binary)
     if (a.endo && full) hipLaunchKernelGGL((keys_bwd_kernel<F, true, true>), dim3(a.groups), dim3(KEYS_WG), a.dfa_bytes, stream, a);
     else if (a.endo) hipLaunchKernelGGL((keys_bwd_kernel<F, false, true>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
     else if (full) hipLaunchKernelGGL((keys_bwd_kernel<FMT, true>), dim3(a.groups), dim3(KEYS_WG), a.dfa_bytes, stream, a);
     else hipLaunchKernelGGL((keys_bwd_kernel<FMT, false>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
     return hipGetLastError();
+    }
 }
 
 // ---- wide fixed-window generator table, built on the device -----------------------------------------------------
@@ -1784,6 +1812,8 @@ hipError_t launch_keys_scan(int fmt, const KeysArgs &a, hipStream_t stream, hipE
         return launch_keys_fmt<VGF_P2PKH_UNCOMPRESSED>(a, stream, before_bwd);
     case VGF_ETHEREUM:
         return launch_keys_fmt<VGF_ETHEREUM>(a, stream, before_bwd);
+    case VGF_ETHEREUM_CONTRACT:
+        return launch_keys_fmt<VGF_ETHEREUM_CONTRACT>(a, stream, before_bwd);
     case VGF_P2TR:
         return launch_keys_fmt<VGF_P2TR>(a, stream, before_bwd);
     default:
@@ -1821,12 +1851,20 @@ static hipError_t launch_bwd(const SeqArgs &a, hipStream_t stream) {
         else hipLaunchKernelGGL((seq_hash_kernel<HF, false>), dim3(a.groups, 2 * a.s / a.hash_kpl), dim3(WG), 0, stream, a);
         return hipGetLastError();
     }
+    if constexpr (DumpOnly<FMT>::value) {   // payloads only: the caller filters them afterwards (launch_payload_filter)
+        constexpr int D = FMT;
+        if (!a.dump) return hipErrorInvalidValue;
+        if (a.endo) hipLaunchKernelGGL((seq_bwd_kernel<D, false, true>), dim3(a.groups), dim3(WG), 0, stream, a);
+        else hipLaunchKernelGGL((seq_bwd_kernel<D, false>), dim3(a.groups), dim3(WG), 0, stream, a);
+        return hipGetLastError();
+    } else {
     if (full && a.endo && FMT != VGF_P2TR) hipLaunchKernelGGL((seq_bwd_kernel<(FMT == VGF_P2TR ? VGF_P2PKH : FMT), true, true>), dim3(a.groups), dim3(WG), a.dfa_bytes, stream, a);
     else if (full) hipLaunchKernelGGL((seq_bwd_kernel<FMT, true>), dim3(a.groups), dim3(WG), a.dfa_bytes, stream, a);
     else if (a.endo && FMT != VGF_P2TR) hipLaunchKernelGGL((seq_bwd_kernel<(FMT == VGF_P2TR ? VGF_P2PKH : FMT), false, true>), dim3(a.groups), dim3(WG), 0, stream, a);
     else if (a.lone && FMT == VGF_P2PKH) hipLaunchKernelGGL((seq_bwd_kernel<VGF_P2PKH, false, false, true>), dim3(a.groups), dim3(WG), 0, stream, a);   // (nearly) alone on the device: the twin without yields
     else hipLaunchKernelGGL((seq_bwd_kernel<FMT, false>), dim3(a.groups), dim3(WG), 0, stream, a);
     return hipGetLastError();
+    }
 }
 
 
@@ -1851,6 +1889,8 @@ hipError_t launch_seq_bwd(int fmt, const SeqArgs &a, hipStream_t stream) {
         return launch_bwd<VGF_P2PKH_UNCOMPRESSED>(a, stream);
     case VGF_ETHEREUM:
         return launch_bwd<VGF_ETHEREUM>(a, stream);
+    case VGF_ETHEREUM_CONTRACT:
+        return launch_bwd<VGF_ETHEREUM_CONTRACT>(a, stream);
     case VGF_P2TR:
         return launch_bwd<VGF_P2TR>(a, stream);
     default:
@@ -1950,10 +1990,39 @@ __global__ void __launch_bounds__(PTAB_COMPACT_WG) ptab_compact_kernel(const Pta
     if (threadIdx.x == 0) a.mhdr->count = start + run;   // plain store: the only writer of the header in this dispatch
 }
 
+// The filter of a DumpOnly format, run over the payloads its per-key kernel wrote: one thread per slot evaluates the context's
+// prefilter (or, FULL, walks the pattern's automaton staged in LDS) and the wave stores its ballot into the hit mask, exactly
+// as ptab_lookup_kernel does; ptab_compact_kernel follows.  An all-zero payload is the dump's "no key" mark: never a hit.
+template <bool FULL>
+__global__ void __launch_bounds__(256) payload_filter_kernel(const PtabArgs a) {
+    extern __shared__ u32 dyn_lds[];
+    if (FULL) {
+        for (u32 i = threadIdx.x; i < a.dfa_bytes / 4; i += 256u) dyn_lds[i] = a.dfa_blob[i];
+        __syncthreads();
+    }
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    const size_t slot = (size_t)blockIdx.y * a.stride + i;
+    bool hit = false;
+    if (i < a.count) {
+        const u32 *p = a.payloads + slot * 5;
+        u32 pl[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) pl[k] = p[k];
+        hit = (pl[0] | pl[1] | pl[2] | pl[3] | pl[4]) != 0u && (FULL ? dfa_match_payload_n<5>(dyn_lds, (int)a.fmt, pl) : filter_eval_n<5>(a.filter, pl));
+    }
+    const unsigned long long m = __ballot(hit);
+    if ((threadIdx.x & 63u) == 0) a.hits[slot >> 6] = m;
+}
+
 hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream) {
-    if (a.stride % 256 != 0 || a.count > a.stride || a.images == 0 || a.tab.bits < 1 || a.tab.bits > 24) return hipErrorInvalidValue;
+    if (a.stride % 256 != 0 || a.count > a.stride || a.images == 0) return hipErrorInvalidValue;
     const dim3 grid(a.stride / 256, a.images);
-    if (payload_words == 8) hipLaunchKernelGGL((ptab_lookup_kernel<8>), grid, dim3(256), 0, stream, a);
+    if (a.filter) {   // a DumpOnly format's own filter instead of a list's table
+        if (payload_words != 5 || a.dfa_bytes > DFA_MAX_BYTES) return hipErrorInvalidValue;
+        if (a.dfa_bytes) hipLaunchKernelGGL((payload_filter_kernel<true>), grid, dim3(256), a.dfa_bytes, stream, a);
+        else hipLaunchKernelGGL((payload_filter_kernel<false>), grid, dim3(256), 0, stream, a);
+    } else if (a.tab.bits < 1 || a.tab.bits > 24) return hipErrorInvalidValue;
+    else if (payload_words == 8) hipLaunchKernelGGL((ptab_lookup_kernel<8>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((ptab_lookup_kernel<5>), grid, dim3(256), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

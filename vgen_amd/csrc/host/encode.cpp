@@ -299,6 +299,7 @@ std::string address_from_payload(uint32_t format, const uint8_t *payload) {
     case VGF_P2TR:
         return segwit_address("bc", 1, payload, 32);
     case VGF_ETHEREUM:
+    case VGF_ETHEREUM_CONTRACT:
         return eip55_address(payload);
     default:
         return std::string();
@@ -306,7 +307,7 @@ std::string address_from_payload(uint32_t format, const uint8_t *payload) {
 }
 
 std::string key_to_wif(uint32_t format, const uint8_t key_be[32]) {
-    if (format == VGF_ETHEREUM) return hex_lower(key_be, 32);
+    if (vgf_is_eth((int)format)) return hex_lower(key_be, 32);
     uint8_t buf[34];
     buf[0] = 0x80;
     memcpy(buf + 1, key_be, 32);
@@ -357,6 +358,14 @@ int payload_from_key(uint32_t format, const uint8_t key_be[32], uint8_t out[32])
         host_keccak256(pub65 + 1, 64, kk);
         memcpy(out, kk + 12, 20);
         return 20;
+    case VGF_ETHEREUM_CONTRACT: {   // the account as above, then the single-source second block (core/hash.h)
+        host_keccak256(pub65 + 1, 64, kk);
+        u32 acc[5], c[5];
+        memcpy(acc, kk + 12, 20);
+        keccak256_create_addr(acc, c);
+        memcpy(out, c, 20);
+        return 20;
+    }
     case VGF_P2TR: {
         // BIP-341 key path, no script tree (address.rs:136-140): the single-source device algorithm
         static std::vector<uint32_t> tab;

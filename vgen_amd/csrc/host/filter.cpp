@@ -538,7 +538,8 @@ bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t 
         if (out.dev.kind == DEVF_HOST_ALL && build_dfa_blob(out.dfa, "bc1q", BECH32, out.dfa_blob)) out.dev.kind = DEVF_DFA;
         break;
     }
-    case VGF_ETHEREUM: {
+    case VGF_ETHEREUM:
+    case VGF_ETHEREUM_CONTRACT: {   // (the contract address is an address string like the account's)
         // EIP-55 casing depends on a second Keccak the kernel does not compute: derive the device
         // test from the case-insensitive language (a superset); the host confirms with the exact DFA.
         Dfa folded;
@@ -614,7 +615,7 @@ bool list_ranges(const std::string &pattern, bool ci, uint32_t format, uint32_t 
     Dfa d;
     std::string err;
     // Ethereum: the device sees the payload, not the EIP-55 casing: ranges of the case-folded language (the host confirms)
-    if (!regex_compile(pattern, ci || format == VGF_ETHEREUM, d, err)) {
+    if (!regex_compile(pattern, ci || vgf_is_eth((int)format), d, err)) {
         why = err;
         return false;
     }
@@ -652,10 +653,11 @@ bool list_ranges(const std::string &pattern, bool ci, uint32_t format, uint32_t 
             return false;
         }
         for (auto &r : ranges) out.push_back({top64_of160(r.lo), top64_of160(r.hi), index});
-    } else if (format == VGF_P2WPKH || format == VGF_P2TR || format == VGF_ETHEREUM) {
-        const char *head = format == VGF_ETHEREUM ? "0x" : format == VGF_P2TR ? "bc1p" : "bc1q";
-        const char *alphabet = format == VGF_ETHEREUM ? HEXL : BECH32;
-        const unsigned bits = format == VGF_ETHEREUM ? 4 : 5, n_data = format == VGF_ETHEREUM ? 40 : format == VGF_P2TR ? 52 : 32;
+    } else if (format == VGF_P2WPKH || format == VGF_P2TR || vgf_is_eth((int)format)) {
+        const bool eth = vgf_is_eth((int)format);
+        const char *head = eth ? "0x" : format == VGF_P2TR ? "bc1p" : "bc1q";
+        const char *alphabet = eth ? HEXL : BECH32;
+        const unsigned bits = eth ? 4 : 5, n_data = eth ? 40 : format == VGF_P2TR ? 52 : 32;
         uint32_t st = 0;
         for (const char *h = head; *h && !d.match_now[st]; h++) st = step(d, st, (unsigned char)*h);
         if (d.match_now[st]) {
@@ -860,7 +862,7 @@ bool payload_from_address(uint32_t format, const std::string &address, uint8_t o
             if (carry) return false;
         }
         memcpy(out, v + 1, 20);
-    } else if (format == VGF_ETHEREUM) {
+    } else if (vgf_is_eth((int)format)) {
         if (a.size() != 42 || a[0] != '0' || (a[1] != 'x' && a[1] != 'X')) return false;
         for (int i = 0; i < 20; i++) {
             int hv[2];

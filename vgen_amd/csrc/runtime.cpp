@@ -251,7 +251,7 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
         err = "device index out of range";
         return VGEN_E_NODEVICE;
     }
-    if (p->format > VGF_ETHEREUM) {
+    if (p->format > VGF_ETHEREUM_CONTRACT) {
         err = "unknown address format";
         return VGEN_E_INVALID;
     }
@@ -568,6 +568,9 @@ int ensure_dump_frame(vgen_ctx *c, uint32_t frame) {
 
 bool dump_mode(const vgen_ctx *c) { return !c->have_filter || c->h_filter.kind == DEVF_HOST_ALL; }
 bool list_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind == DEVF_LIST; }
+// The Ethereum-contract kernels only write payloads (kernels.hip: DumpOnly): a pattern's device filter runs behind them over
+// the frame's device-only payload buffer and the list path's compaction makes the records.
+bool deferred_filter(const vgen_ctx *c) { return c->format == VGF_ETHEREUM_CONTRACT && c->have_filter && !dump_mode(c) && !list_mode(c); }
 
 // The pattern-list buffers of every frame: the payloads of a dispatch (20 B per key, x 6 on an endomorphism context, 32 B for
 // P2TR) and the hit mask (one bit per slot).  Device memory only — the payloads never leave the device — so, unlike dump mode,
@@ -620,7 +623,16 @@ int upload_ptab(vgen_ctx *c, const PatternList &L) {
 int enqueue_ptab(vgen_ctx *c, vgen_ctx::Frame &f, uint32_t count, bool endo) {
     PtabArgs p;
     memset(&p, 0, sizeof p);
-    p.tab = c->ptab;
+    if (deferred_filter(c)) {
+        p.filter = c->d_filter;
+        if (c->h_filter.kind == DEVF_DFA) {
+            p.dfa_blob = c->h_filter.dfa_blob;
+            p.dfa_bytes = c->h_filter.dfa_bytes;
+        }
+        p.fmt = (uint32_t)vgf_string_format((int)c->format);
+    } else {
+        p.tab = c->ptab;
+    }
     p.payloads = f.d_list;
     p.hits = f.d_hits;
     p.mhdr = reinterpret_cast<DevMatchHeader *>(f.d_match);
@@ -674,6 +686,7 @@ int rt_set_filter(vgen_ctx *c, const vgen_filter *f) {
     if (int rc = upload(c, c->d_filter, &c->h_filter, sizeof(DevFilter))) return rc;
     c->have_filter = true;
     if (dump_mode(c)) return ensure_dump_slab(c);
+    if (deferred_filter(c)) return ensure_list_slab(c);
     return VGEN_OK;
 }
 
@@ -1199,20 +1212,20 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
         for (int i = 0; i < 8; i++) a.base[i] = base->w[i];
     a.filter = c->d_filter;
     a.n = n;
-    a.fmt = c->format;
+    a.fmt = (uint32_t)vgf_string_format((int)c->format);   // what the on-device matcher spells the payload as
     const uint32_t max_groups = (c->batch + KEYS_WG - 1) / KEYS_WG;
     a.groups = (n + KEYS_WG - 1) / KEYS_WG;
     a.xyz = f.d_keys_scratch;
     a.tree = a.xyz + (size_t)27 * max_groups * KEYS_WG;
     a.root = a.tree + (size_t)max_groups * 9 * KEYS_WG;
     const bool dump = dump_mode(c);
-    if (c->h_filter.kind == DEVF_DFA && !dump) a.dfa_bytes = c->h_filter.dfa_bytes;
+    if (c->h_filter.kind == DEVF_DFA && !dump && !deferred_filter(c)) a.dfa_bytes = c->h_filter.dfa_bytes;
     // endomorphism contexts: six images per scalar multiplication here too (see rt_dispatch for the LDS rule)
-    const bool parks_y = c->format == VGF_P2PKH_UNCOMPRESSED || c->format == VGF_ETHEREUM;
+    const bool parks_y = c->format == VGF_P2PKH_UNCOMPRESSED || vgf_is_eth((int)c->format);
     const bool endo_now = c->endo && !(a.dfa_bytes && parks_y && a.dfa_bytes + 2u * 9u * KEYS_WG * 4u > 64u * 1024u);
     a.endo = endo_now ? 1u : 0u;
     a.vstride = c->batch;
-    const bool listed = list_mode(c);
+    const bool listed = list_mode(c) || deferred_filter(c);
     if (dump) {
         if (int rc = ensure_dump_frame(c, (uint32_t)(&f - c->fr.data()))) return rc;
         if (n < c->batch) HIP_TRY(c, hipMemsetAsync(f.d_dump, 0, (size_t)c->batch * (endo_now ? 6 : 1) * c->payload_words * sizeof(uint32_t), f.s));
@@ -1302,7 +1315,7 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
         a.lone = others <= c->lone_max_others;
     }
     const bool dump = dump_mode(c);
-    const bool listed = list_mode(c);
+    const bool listed = list_mode(c) || deferred_filter(c);
     if (dump) {
         if (int rc = ensure_dump_frame(c, (uint32_t)(&f - c->fr.data()))) return rc;
         a.dump = f.d_dump;
@@ -1318,11 +1331,11 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
             a.dfa_bytes = c->h_filter.dfa_bytes;
         }
     }
-    a.fmt = c->format;
+    a.fmt = (uint32_t)vgf_string_format((int)c->format);   // what the on-device matcher spells the payload as
     // six images per point (every format but P2TR: c->endo is never set there), whatever the filter — unless the
     // pattern's automaton leaves no room in a workgroup's 64 KiB of LDS for the y coordinate the uncompressed / Ethereum
     // formats park beside the product tree (2 x 9 KiB static + the blob): such a dispatch tests the plain keys
-    const bool parks_y = c->format == VGF_P2PKH_UNCOMPRESSED || c->format == VGF_ETHEREUM;
+    const bool parks_y = c->format == VGF_P2PKH_UNCOMPRESSED || vgf_is_eth((int)c->format);
     const bool endo_now = c->endo && !(a.dfa_bytes && parks_y && a.dfa_bytes + 2u * 9u * SEQ_WG * 4u > 64u * 1024u);
     a.endo = endo_now ? 1u : 0u;
     if (c->format == VGF_P2TR) {   // the tweak multiplication t*G needs the fixed-window table ...
