@@ -71,8 +71,8 @@ static vgen_scan_config range_cfg(uint32_t fmt, uint64_t lo, uint64_t hi, uint64
     return c;
 }
 
-// the oracle's matches of [lo, hi], sorted by key
-static Pairs oracle_range(int fmt, const char *pat, int ci, uint64_t lo, uint64_t hi) {
+// the oracle's matches of [lo, hi], sorted by key; `keys` (optional): their big-endian keys, beside them
+static Pairs oracle_range(int fmt, const char *pat, int ci, uint64_t lo, uint64_t hi, std::vector<std::string> *keys = nullptr) {
     uint8_t a[32], b[32];
     key_of(lo, a);
     key_of(hi, b);
@@ -81,6 +81,8 @@ static Pairs oracle_range(int fmt, const char *pat, int ci, uint64_t lo, uint64_
     Pairs out;
     CHECK(rc == 0, "vo_scan_range rc=%d", rc);
     for (size_t i = 0; i < r.n_matches; i++) out.emplace_back(r.matches[i].gen.address, r.matches[i].gen.wif);
+    if (keys)
+        for (size_t i = 0; i < r.n_matches; i++) keys->emplace_back((const char *)r.matches[i].key, 32);
     vo_scan_free(&r);
     return out;
 }
@@ -490,6 +492,251 @@ static void sc_edge_ranges() {
     for (auto *x : cs) vgen_destroy(x);
 }
 
+// ---- pattern lists (vgen_scan_list) ------------------------------------------------------------------------------
+
+// What the oracle says about a list over a key range: per key (big-endian, so the map's order is the walk's) its address
+// and the patterns it satisfies — one oracle_range per pattern, nothing of the product's list code involved.
+struct ListHit {
+    std::string address, wif;
+    std::vector<uint32_t> which;   // ascending
+};
+using ListHits = std::map<std::string, ListHit>;
+
+static ListHits oracle_list(int fmt, const std::vector<std::string> &pats, int ci, uint64_t lo, uint64_t hi) {
+    ListHits hits;
+    for (uint32_t p = 0; p < pats.size(); p++) {
+        std::vector<std::string> keys;
+        const Pairs m = oracle_range(fmt, pats[p].c_str(), ci, lo, hi, &keys);
+        for (size_t i = 0; i < m.size(); i++) {
+            ListHit &h = hits[keys[i]];
+            h.address = m[i].first;
+            h.wif = m[i].second;
+            h.which.push_back(p);
+        }
+    }
+    return hits;
+}
+
+// The rule of include/vgen_hip.h (vgen_scan_list) replayed over the walk: a key is reported once, counts toward every
+// pattern it satisfies, is skipped when every pattern it satisfies already has per_pattern matches; the scan stops at
+// `count` or when all patterns are satisfied.
+struct ListWant {
+    Pairs pairs;
+    std::vector<std::vector<uint32_t>> which;
+    std::vector<std::string> keys;
+};
+static ListWant replay_list(const ListHits &hits, size_t n_patterns, uint64_t per_pattern, uint64_t count) {
+    ListWant w;
+    std::vector<uint64_t> got(n_patterns, 0);
+    size_t unsatisfied = n_patterns;
+    for (auto &kv : hits) {
+        if (w.pairs.size() >= count || (per_pattern && unsatisfied == 0)) break;
+        bool wanted = per_pattern == 0;
+        for (uint32_t p : kv.second.which) wanted = wanted || got[p] < per_pattern;
+        if (!wanted) continue;
+        for (uint32_t p : kv.second.which)
+            if (++got[p] == per_pattern) unsatisfied--;
+        w.pairs.emplace_back(kv.second.address, kv.second.wif);
+        w.which.push_back(kv.second.which);
+        w.keys.push_back(kv.first);
+    }
+    return w;
+}
+
+static vgen_filter *make_list(const std::vector<std::string> &pats, int ci, uint32_t fmt) {
+    std::string text;
+    for (auto &p : pats) text += p + "\n";
+    vgen_filter *f = nullptr;
+    const int rc = vgen_filter_compile_list(text.c_str(), ci, fmt, &f);
+    CHECK(rc == VGEN_OK && f, "vgen_filter_compile_list rc=%d %s", rc, vgen_last_error(nullptr));
+    return f;
+}
+
+// the result list, order included, and vgen_filter_which of every result
+static void check_list(const char *what, const vgen_filter *f, const vgen_scan_result &r, const ListWant &w) {
+    CHECK(got_of(r) == w.pairs, "%s: %llu results, the rule over the oracle's matches gives %zu", what, (unsigned long long)r.n_matches, w.pairs.size());
+    for (uint64_t i = 0; i < r.n_matches && i < w.which.size(); i++) {
+        uint32_t idx[16], n = 0;
+        const int rc = vgen_filter_which(f, r.matches[i].address, idx, 16, &n);
+        CHECK(rc == VGEN_OK && n <= 16 && std::vector<uint32_t>(idx, idx + n) == w.which[i], "%s: vgen_filter_which of result %llu (%s)", what,
+              (unsigned long long)i, r.matches[i].address);
+    }
+}
+
+// Results that no oracle walk names in advance (random bases, random keys): every one is a valid key, no key twice, each
+// satisfies a pattern that still wanted matches when it was taken, and no scan goes on beyond what the rule allows.
+static void check_list_rule(const char *what, const vgen_filter *f, uint32_t fmt, size_t n_patterns, uint64_t per_pattern, uint64_t count, const vgen_scan_result &r) {
+    std::vector<uint64_t> got(n_patterns, 0);
+    size_t unsatisfied = n_patterns;
+    CHECK(r.n_matches <= count, "%s: %llu results beyond count", what, (unsigned long long)r.n_matches);
+    for (uint64_t i = 0; i < r.n_matches; i++) {
+        vo_generated g;
+        CHECK(vo_generate((int)fmt, r.matches[i].key, &g) && !strcmp(g.address, r.matches[i].address) && !strcmp(g.wif, r.matches[i].wif), "%s: result %llu does not re-derive",
+              what, (unsigned long long)i);
+        for (uint64_t j = 0; j < i; j++) CHECK(memcmp(r.matches[i].key, r.matches[j].key, 32) != 0, "%s: duplicate key %llu/%llu", what, (unsigned long long)i, (unsigned long long)j);
+        uint32_t idx[16], n = 0;
+        CHECK(vgen_filter_which(f, r.matches[i].address, idx, 16, &n) == VGEN_OK && n >= 1 && n <= 16, "%s: result %llu satisfies no pattern", what, (unsigned long long)i);
+        CHECK(!per_pattern || unsatisfied > 0, "%s: result %llu after every pattern was satisfied", what, (unsigned long long)i);
+        bool wanted = per_pattern == 0;
+        for (uint32_t k = 0; k < n && k < 16; k++) wanted = wanted || got[idx[k]] < per_pattern;
+        CHECK(wanted, "%s: result %llu (%s) satisfies only patterns that had their %llu matches", what, (unsigned long long)i, r.matches[i].address,
+              (unsigned long long)per_pattern);
+        for (uint32_t k = 0; k < n && k < 16; k++)
+            if (++got[idx[k]] == per_pattern) unsatisfied--;
+    }
+}
+
+static std::string temp_path(const char *tmpl) {
+    std::string path(tmpl);
+    int fd = mkstemp(&path[0]);
+    close(fd);
+    unlink(path.c_str());
+    return path;
+}
+
+static void sc_pattern_list() {
+    // overlapping prefixes (a key of "^1Bcd" also counts for "^1Bc" and "^1B"), frequent and rare ones, and one that the
+    // range does not satisfy often enough, so that a per-pattern bound alone does not end the scan early
+    const std::vector<std::string> pats = {"^1B", "^1Bc", "^1A[a-f]", "^1[C-D]x", "^1Bcd", "^1Efg", "^1Zzzzz"};
+    const uint64_t lo = 0xD0000, hi = lo + 9ull * BATCH - 1 - 55;
+    const ListHits hits = oracle_list(0, pats, 0, lo, hi);
+    vgen_filter *f = make_list(pats, 0, 0);
+    if (!f) return;
+    const ListWant all = replay_list(hits, pats.size(), 0, UINT64_MAX);
+    // (what the cases below rest on: matches in several batches, keys that satisfy more than one pattern)
+    size_t multi = 0;
+    for (auto &w : all.which) multi += w.size() > 1;
+    CHECK(all.pairs.size() > 300 && multi > 10, "the oracle's list matches: %zu, %zu of them of several patterns", all.pairs.size(), multi);
+
+    struct Case { uint64_t per_pattern, count; };
+    const Case cases[] = {{1, UINT64_MAX}, {2, UINT64_MAX}, {0, UINT64_MAX}, {0, 40}, {2, 7}};
+    std::vector<ListWant> wants;
+    for (auto &k : cases) wants.push_back(replay_list(hits, pats.size(), k.per_pattern, k.count));
+    {
+        // per_pattern 1 and 2 reach into later batches (the rare patterns), and skip keys on the way
+        uint8_t b1[32];
+        key_of(lo + BATCH, b1);
+        const std::string second_batch((const char *)b1, 32);
+        CHECK(!wants[0].keys.empty() && wants[0].keys.back() >= second_batch && wants[0].pairs.size() < wants[1].pairs.size() && wants[1].pairs.size() < all.pairs.size(),
+              "per_pattern 1 / 2 / 0: %zu / %zu / %zu results", wants[0].pairs.size(), wants[1].pairs.size(), all.pairs.size());
+    }
+    // one context, and three striped ones: the same results in the same order
+    for (uint32_t n_ctx : {1u, 3u}) {
+        vgen_ctx *cs[3] = {make_ctx(0, 3), n_ctx > 1 ? make_ctx(0, 2) : nullptr, n_ctx > 1 ? make_ctx(0, 4) : nullptr};
+        for (size_t k = 0; k < sizeof cases / sizeof cases[0]; k++) {
+            vgen_scan_config cfg = range_cfg(0, lo, hi, cases[k].count);
+            vgen_scan_result r;
+            CbLog log;
+            const int rc = vgen_scan_list(cs, n_ctx, f, cases[k].per_pattern, &cfg, cb_log, &log, nullptr, &r);
+            char what[128];
+            snprintf(what, sizeof what, "list, %u context(s), per_pattern %llu, count %lld", n_ctx, (unsigned long long)cases[k].per_pattern, (long long)cases[k].count);
+            CHECK(rc == VGEN_OK && r.failed_shards == 0, "%s: rc=%d %s", what, rc, vgen_last_error(cs[0]));
+            check_list(what, f, r, wants[k]);
+            for (size_t i = 0; i < log.seen.size(); i++) CHECK(log.seen[i] == (i + 1) * (uint64_t)BATCH, "%s: callback %zu = %llu", what, i, (unsigned long long)log.seen[i]);
+            CHECK(!log.seen.empty() && log.seen.back() == r.operations, "%s: last callback", what);
+            if (cases[k].count == UINT64_MAX)   // ("^1Zzzzz" is never satisfied: the whole range is walked)
+                CHECK(r.complete == 1 && r.operations == 9ull * BATCH, "%s: complete=%d ops=%llu", what, r.complete, (unsigned long long)r.operations);
+            vgen_scan_result_free(&r);
+        }
+        for (uint32_t i = 0; i < n_ctx; i++) vgen_destroy(cs[i]);
+    }
+    // checkpoint: stopped by max_batches, resumed — the uninterrupted scan's result; one context (its record is the walk's
+    // order), and three (earlier runs' matches come first, in the order they were recorded: the same set)
+    for (uint32_t n_ctx : {1u, 3u}) {
+        for (uint64_t pp : {2ull, 0ull}) {
+            if (n_ctx > 1 && pp) continue;
+            const std::string path = temp_path("/tmp/vgen_fake_lck_XXXXXX");
+            vgen_ctx *cs[3] = {make_ctx(0, 3), n_ctx > 1 ? make_ctx(0, 2) : nullptr, n_ctx > 1 ? make_ctx(0, 2) : nullptr};
+            vgen_scan_config cfg = range_cfg(0, lo, hi);
+            cfg.checkpoint_path = path.c_str();
+            cfg.checkpoint_interval_ms = 1;
+            cfg.max_batches = n_ctx == 1 ? 4 : 2;
+            vgen_scan_result r;
+            int rc = vgen_scan_list(cs, n_ctx, f, pp, &cfg, nullptr, nullptr, nullptr, &r);
+            const uint64_t leg1 = n_ctx == 1 ? 4 : 6;
+            CHECK(rc == VGEN_OK && r.complete == 0 && r.operations == leg1 * BATCH, "list checkpoint leg 1 (%u ctx): rc=%d complete=%d ops=%llu", n_ctx, rc, r.complete,
+                  (unsigned long long)r.operations);
+            const uint64_t first = r.n_matches;
+            vgen_scan_result_free(&r);
+            cfg.max_batches = 0;
+            rc = vgen_scan_list(cs, n_ctx, f, pp, &cfg, nullptr, nullptr, nullptr, &r);
+            const ListWant &want = pp ? wants[1] : all;
+            CHECK(rc == VGEN_OK && r.complete == 1 && r.resumed_operations == leg1 * BATCH && r.operations == (9 - leg1) * BATCH && first > 0 && first < r.n_matches,
+                  "list checkpoint leg 2 (%u ctx): rc=%d complete=%d ops=%llu+%llu n=%llu then %llu", n_ctx, rc, r.complete, (unsigned long long)r.resumed_operations,
+                  (unsigned long long)r.operations, (unsigned long long)first, (unsigned long long)r.n_matches);
+            if (n_ctx == 1) {
+                check_list("list checkpoint, resumed", f, r, want);
+            } else {
+                Pairs a = got_of(r), b = want.pairs;
+                std::sort(a.begin(), a.end());
+                std::sort(b.begin(), b.end());
+                CHECK(a == b, "list checkpoint over three contexts: %zu results, want %zu", a.size(), b.size());
+            }
+            vgen_scan_result_free(&r);
+            // the same file under another list: refused
+            std::vector<std::string> other_pats(pats.begin(), pats.end() - 1);
+            vgen_filter *other = make_list(other_pats, 0, 0);
+            rc = vgen_scan_list(cs, n_ctx, other, pp, &cfg, nullptr, nullptr, nullptr, &r);
+            CHECK(rc == VGEN_E_INVALID, "a checkpoint written for another list: rc=%d", rc);
+            vgen_scan_result_free(&r);
+            vgen_filter_free(other);
+            unlink(path.c_str());
+            for (uint32_t i = 0; i < n_ctx; i++) vgen_destroy(cs[i]);
+        }
+    }
+    // one of three contexts fails: the survivors take its slot over, the result is the one-context result
+    for (int victim = 0; victim < 3; victim++) {
+        for (size_t k : {(size_t)(1 + victim % 2)}) {
+            vgen_ctx *cs[3] = {make_ctx(0, 2), make_ctx(0, 3), make_ctx(0, 2)};
+            vgen_debug_fail_after(cs[victim], 1 + (uint64_t)victim % 2);   // (each slot has three batches)
+            vgen_scan_config cfg = range_cfg(0, lo, hi);
+            vgen_scan_result r;
+            const int rc = vgen_scan_list(cs, 3, f, cases[k].per_pattern, &cfg, nullptr, nullptr, nullptr, &r);
+            CHECK(rc == VGEN_OK && r.failed_shards == 1 && r.complete == 1, "list take-over, victim %d: rc=%d failed=%d complete=%d %s", victim, rc, r.failed_shards, r.complete,
+                  vgen_last_error(cs[0]));
+            check_list("list take-over", f, r, wants[k]);
+            vgen_scan_result_free(&r);
+            for (auto *c : cs) vgen_destroy(c);
+        }
+    }
+    vgen_filter_free(f);
+    // contexts that walk from bases of their own (endomorphism images: results in arrival order) and random keys (streams
+    // striped over the contexts): no walk to compare with, the rule must hold over the results as they come
+    const std::vector<std::string> easy = {"^1A", "^1B", "^1C[a-m]", "^1C"};
+    vgen_filter *fe = make_list(easy, 0, 0);
+    if (!fe) return;
+    for (uint32_t flags : {(uint32_t)VGEN_FLAG_ENDO, 0u}) {
+        for (uint32_t n_ctx : {1u, 3u}) {
+            if (flags && n_ctx == 1) continue;
+            vgen_ctx *cs[3] = {make_ctx(0, 2, 0, flags), n_ctx > 1 ? make_ctx(0, 3, 0, flags) : nullptr, n_ctx > 1 ? make_ctx(0, 2, 0, flags) : nullptr};
+            for (const Case &k : {Case{3, UINT64_MAX}, Case{0, 25}}) {
+                vgen_scan_config cfg;
+                memset(&cfg, 0, sizeof cfg);
+                cfg.struct_size = sizeof cfg;
+                cfg.count = k.count;
+                cfg.max_batches = 4;
+                if (!flags) {
+                    cfg.flags = VGEN_SCAN_RANDOM_KEYS;
+                    cfg.seed = 4242;
+                }
+                vgen_scan_result r;
+                const int rc = vgen_scan_list(cs, n_ctx, fe, k.per_pattern, &cfg, nullptr, nullptr, nullptr, &r);
+                char what[128];
+                snprintf(what, sizeof what, "list, %s, %u context(s), per_pattern %llu, count %lld", flags ? "endomorphism contexts" : "random keys", n_ctx,
+                         (unsigned long long)k.per_pattern, (long long)k.count);
+                CHECK(rc == VGEN_OK && r.n_matches > 0, "%s: rc=%d n=%llu %s", what, rc, (unsigned long long)r.n_matches, vgen_last_error(cs[0]));
+                // (one key in eight satisfies the list: four batches hold far more than any of these cases asks for)
+                if (k.per_pattern == 3) CHECK(r.n_matches >= 3 && r.n_matches <= 3 * easy.size(), "%s: %llu results", what, (unsigned long long)r.n_matches);
+                else CHECK(r.n_matches == k.count, "%s: %llu results", what, (unsigned long long)r.n_matches);
+                check_list_rule(what, fe, 0, easy.size(), k.per_pattern, k.count, r);
+                vgen_scan_result_free(&r);
+            }
+            for (uint32_t i = 0; i < n_ctx; i++) vgen_destroy(cs[i]);
+        }
+    }
+    vgen_filter_free(fe);
+}
+
 // Randomised differential: formats x pattern kinds (hash160 ranges, bit masks, on-device automaton, full dumps filtered on the
 // host, NFA-walk patterns) x ranges cut anywhere x counts x one to three contexts x frames x ring sizes x injected failures,
 // every result against the oracle's scan of the same range.  VGEN_FAKE_FUZZ_SEED / VGEN_FAKE_FUZZ_CASES select the walk.
@@ -629,6 +876,50 @@ static void sc_fuzz() {
         CHECK(r.failed_shards == 0 || (victim >= 0 && !with_ck && r.failed_shards == 1), "%s: failed_shards=%d", what, r.failed_shards);
         vgen_scan_result_free(&r);
         for (uint32_t i = 0; i < n_ctx; i++) vgen_destroy(cs[i]);
+        // every third such case: a pattern list over the same range (vgen_scan_list), one to three fresh contexts, sometimes
+        // one that fails — the rule of vgen_hip.h over the oracle's matches, order included whatever the contexts.  (Drawn
+        // after everything above, from a generator of its own seeded by this one's state: the cases above stay what they were.)
+        uint64_t saved = x;
+        x ^= 0x9E3779B97F4A7C15ull;
+        if (rnd(3) == 0) {
+            struct ListPats { uint32_t fmt; int ci; std::vector<std::string> pats; };
+            static const ListPats lists[] = {
+                {0, 0, {"^1A", "^1B[a-k]", "^1Bc", "^1Cd", "^1[D-F]xy"}},
+                {0, 0, {"^1[A-H]", "^1Jk"}},                       // a third of all keys: dumps filtered on the host
+                {0, 1, {"^1ab", "^1c"}},
+                {2, 0, {"^3A", "^3[B-C]z", "^3Bz"}},
+                {5, 0, {"^0x1", "^0x12", "^0x[2-3]4"}},
+                {1, 0, {"^bc1qa", "^bc1q[c-e]x"}},
+            };
+            const ListPats &lp = lists[rnd(sizeof lists / sizeof lists[0])];
+            static const uint64_t pps[] = {0, 1, 2, 5}, lcounts[] = {4, 60, UINT64_MAX, UINT64_MAX};
+            const uint64_t pp = pps[rnd(4)], lcount = lcounts[rnd(4)];
+            const uint32_t ln = 1 + (uint32_t)rnd(3), lcap = rnd(2) ? 0 : 256;
+            vgen_ctx *lc[3] = {nullptr, nullptr, nullptr};
+            for (uint32_t i = 0; i < ln; i++) lc[i] = make_ctx(lp.fmt, 2 + (uint32_t)rnd(4), lcap);
+            int lvictim = -1;
+            if (ln > 1 && rnd(3) == 0) {
+                lvictim = (int)rnd(ln);
+                vgen_debug_fail_after(lc[lvictim], rnd(3));
+            }
+            vgen_filter *lf = make_list(lp.pats, lp.ci, lp.fmt);
+            if (lf) {
+                const ListWant lw = replay_list(oracle_list((int)lp.fmt, lp.pats, lp.ci, lo, hi), lp.pats.size(), pp, lcount);
+                vgen_scan_config lcfg = range_cfg(lp.fmt, lo, hi, lcount);
+                vgen_scan_result lr;
+                const int lrc = vgen_scan_list(lc, ln, lf, pp, &lcfg, nullptr, nullptr, nullptr, &lr);
+                char lwhat[256];
+                snprintf(lwhat, sizeof lwhat, "case %d: list fmt %u '%s',...%s [%llx, +%llu] per_pattern %llu count %lld ctx %u cap %u victim %d: rc=%d", t, lp.fmt,
+                         lp.pats[0].c_str(), lp.ci ? " -i" : "", (unsigned long long)lo, (unsigned long long)len, (unsigned long long)pp, (long long)lcount, ln, lcap, lvictim, lrc);
+                CHECK(lrc == VGEN_OK, "%s: %s", lwhat, vgen_last_error(lc[0]));
+                check_list(lwhat, lf, lr, lw);
+                CHECK(lr.failed_shards == 0 || (lvictim >= 0 && lr.failed_shards == 1), "%s: failed_shards=%d", lwhat, lr.failed_shards);
+                vgen_scan_result_free(&lr);
+                vgen_filter_free(lf);
+            }
+            for (uint32_t i = 0; i < ln; i++) vgen_destroy(lc[i]);
+        }
+        x = saved;
     }
 }
 
@@ -636,7 +927,8 @@ int main(int argc, char **argv) {
     const std::map<std::string, std::function<void()>> all = {
         {"range_scan", sc_range_scan}, {"stop_flag", sc_stop_flag}, {"checkpoint", sc_checkpoint}, {"multi_context", sc_multi_context},
         {"ring_growth", sc_ring_growth_and_host_filter}, {"failure_takeover", sc_failure_takeover}, {"random_keys", sc_random_keys},
-        {"endo_and_formats", sc_endo_and_formats}, {"dispatch_api", sc_dispatch_api}, {"edge_ranges", sc_edge_ranges}, {"fuzz", sc_fuzz}, {"random_checkpoint", sc_random_checkpoint}};
+        {"endo_and_formats", sc_endo_and_formats}, {"dispatch_api", sc_dispatch_api}, {"edge_ranges", sc_edge_ranges}, {"fuzz", sc_fuzz}, {"random_checkpoint", sc_random_checkpoint},
+        {"pattern_list", sc_pattern_list}};
     std::vector<std::string> run;
     for (int i = 1; i < argc; i++) run.push_back(argv[i]);
     if (run.empty())

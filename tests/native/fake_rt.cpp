@@ -18,9 +18,11 @@
 #include "../../vgen_amd/csrc/core/dfa_eval.h"
 #include "../../vgen_amd/csrc/core/filter_eval.h"
 #include "../../vgen_amd/csrc/core/hash.h"
+#include "../../vgen_amd/csrc/core/ptab_eval.h"
 #include "../../vgen_amd/csrc/core/rnd.h"
 #include "../../vgen_amd/csrc/core/taproot.h"
 #include "../../vgen_amd/csrc/host/encode.h"
+#include "../../vgen_amd/csrc/host/filter.h"
 #include "../../vgen_amd/csrc/runtime.h"
 
 namespace vg {
@@ -37,6 +39,7 @@ struct FakeFrame {
 struct FakeCtx : vgen_ctx {
     std::vector<FakeFrame> ff;
     std::vector<uint32_t> chk_lut, dfa_blob;   // the filter's tables (host copies the DevFilter points at)
+    std::shared_ptr<PatternList> list;         // DEVF_LIST: the list whose interval table stands in for the device's copy
     unsigned stream_delay_ms = 2;              // what creating a hardware queue costs, scaled down
 };
 
@@ -75,6 +78,7 @@ void payload_words(uint32_t fmt, const fe &x, const fe &y, u32 out[8]) {
 
 bool candidate(const FakeCtx *c, const u32 *pl) {
     const int nw = (int)c->payload_words;
+    if (c->h_filter.kind == DEVF_LIST) return ptab_find(c->list->view(), ptab_top64(pl)) >= 0;   // the kernel's lookup (ptab_lookup_kernel)
     if (c->h_filter.kind == DEVF_DFA)
         return nw == 8 ? dfa_match_payload_n<8>(c->h_filter.dfa_blob, (int)c->format, pl) : dfa_match_payload_n<5>(c->h_filter.dfa_blob, (int)c->format, pl);
     return nw == 8 ? filter_eval_n<8>(&c->h_filter, pl) : filter_eval_n<5>(&c->h_filter, pl);
@@ -357,10 +361,13 @@ int rt_set_filter(vgen_ctx *c0, const vgen_filter *f) {
         if (fr.in_flight) return c->fail(VGEN_E_STATE, "vgen_set_filter while a dispatch is in flight");
     if (!f) {
         c->have_filter = false;
+        c->list.reset();
         return VGEN_OK;
     }
     if (f->format != c->format) return c->fail(VGEN_E_INVALID, "filter was compiled for another address format");
+    if (f->dev.kind == DEVF_LIST && !f->list) return c->fail(VGEN_E_INVALID, "pattern-list filter without its list");
     c->h_filter = f->dev;
+    c->list = f->dev.kind == DEVF_LIST ? f->list : nullptr;   // (records go through the ring, as for the other device kinds)
     c->chk_lut = f->chk_lut;
     c->dfa_blob = f->dfa_blob;
     if (f->dev.chk_lut) c->h_filter.chk_lut = c->chk_lut.data();

@@ -32,7 +32,8 @@ def test_fault_injection_is_not_part_of_the_shipped_library():
     """vgen_debug_fail_after and the VGEN_DEBUG_GTAB_FAIL switch exist only in the test build (tests/native/
     libvgen_hip_hooks.so, the same sources with -DVGEN_TEST_HOOKS): the shipped library exports no debug symbol, reads no
     debug variable, and neither the header nor the reference-side binding in INTEGRATION.md declares one."""
-    from conftest import HOOKS_SO
+    from conftest import HOOKS_SO, locked_make
+    locked_make("-s", "-C", os.path.join(ROOT, "tests", "native"), "libvgen_hip_hooks.so")   # (this test may be the first to need it)
     lib = ctypes.CDLL(os.path.join(ROOT, "vgen_amd", "libvgen_hip.so"))
     assert not hasattr(lib, "vgen_debug_fail_after")
     syms = subprocess.run(["nm", "-D", "--defined-only", os.path.join(ROOT, "vgen_amd", "libvgen_hip.so")], capture_output=True, text=True).stdout

@@ -1,8 +1,8 @@
 """The C driver of tests/native/fake_driver.cpp linked against the REAL libvgen_hip.so (tests/native/scan_driver_hip, built
 by __graft_entry__.build()): the scenarios the host sanitizer runs walk over the CPU stand-in of the runtime — range scans
 with progress, stop flag, checkpoint / resume, striped contexts, ring growth and host-filtered dumps, failing contexts taken
-over, random keys, endomorphism images, the frame-level API, ranges cut anywhere — and its seeded random walk over formats x
-pattern kinds x ranges x counts x contexts x frames x ring sizes x injected failures, here through runtime.cpp and the
+over, random keys, endomorphism images, the frame-level API, ranges cut anywhere, pattern lists (thirteen scenarios) — and its
+seeded random walk over formats x pattern kinds and lists x ranges x counts x contexts x frames x ring sizes x injected failures, here through runtime.cpp and the
 kernels on the MI355X, every result checked against the oracle by the driver itself."""
 import os
 import subprocess
@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 DRIVER = os.path.join(HERE, "native", "scan_driver_hip")
 SCENARIOS = ["range_scan", "stop_flag", "checkpoint", "multi_context", "ring_growth", "failure_takeover", "random_keys",
-             "endo_and_formats", "dispatch_api", "edge_ranges", "fuzz", "random_checkpoint"]
+             "endo_and_formats", "dispatch_api", "edge_ranges", "fuzz", "random_checkpoint", "pattern_list"]
 
 
 # (VGEN_TEST_FULL=1: the second seed's walk as well — rounds 3 and 4 ran both, and 5 400 more cases by hand, without a finding;

@@ -9,20 +9,14 @@
 // Differences, all on the host side of the boundary: candidates arrive pre-filtered by the device and
 // are confirmed with the exact DFA (the reference encodes and regex-matches all batch_size hashes on
 // rayon); the base key can be seeded; batches can be striped over several contexts (multi-GPU).
-#include <fcntl.h>
-#include <sched.h>
 #include <stdlib.h>
 #include <string.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
-#include <functional>
-#include <map>
 #include <mutex>
 #include <memory>
 #include <random>
@@ -30,9 +24,13 @@
 #include <vector>
 
 #include "../../include/vgen_hip.h"
+#include "host/checkpoint.h"
 #include "host/encode.h"
 #include "host/filter.h"
+#include "host/host_pool.h"
+#include "host/list_ledger.h"
 #include "host/scalar.h"
+#include "host/scan_match.h"
 #include "runtime.h"
 
 // -DVGEN_SCAN_PROFILE (tools/permissive_probe.py, profiles/r04_permissive.txt): seconds the scanning thread spends in vgen_wait, in the
@@ -77,7 +75,6 @@ void seed_key(uint64_t seed, uint32_t shard, Scalar &out) {
 
 namespace {
 
-
 void random_valid_key(Scalar &k) {
     std::random_device rd;
     for (;;) {
@@ -85,18 +82,6 @@ void random_valid_key(Scalar &k) {
         if (scalar_is_valid(k)) return;   // rejection sampling, gpu.rs:938-944
     }
 }
-
-// `images`: 1, or 6 when the dispatch tested the endomorphism / negation images of every point: index is then
-// variant * batch + i and the key is variant `index / batch` of batch_start + i (host/scalar.h).
-// How a batch's candidate index maps to its private key: batch_start + index (the walk), or the counter-based stream.
-struct BatchKeys {
-    uint64_t batch_no = 0;   // this shard's batch number (checkpointed batches included)
-    Scalar start{};
-    bool random = false;
-    RndSeed seed{};
-    uint64_t first_index = 0;
-    uint32_t stream = 0;
-};
 
 // The seed of a random-key scan (core/rnd.h): the caller's 64-bit one — reproducible runs and tests, NOT for keys that will
 // hold value — or, unseeded, 192 bits of OS entropy (every key the mode returns is a function of seed, stream and index:
@@ -108,422 +93,6 @@ RndSeed scan_rnd_seed(uint64_t cfg_seed) {
     for (int i = 0; i < 6; i++) s.w[i] = rd();
     return s;
 }
-
-// A confirmed match as the scan loop carries it: the private key and the address string.  WIF and hex are rendered when
-// the match is handed to the caller (finish_result), in parallel and only for the matches that survive `count` — the
-// reference, too, builds its WIF per MATCH, not per candidate (src/gpu.rs:1080-1088).  [Round 3 carried the 276-byte ABI
-// record with everything rendered: on a permissive pattern (`^1C`: one key in 23) more than half of a scan was the serial
-// hand-over of those records and their second Base58Check, profiles/r04_permissive.txt.]
-struct LiteMatch {
-    uint8_t key[32];
-    char address[64];     // NUL-terminated (longest: a 62-character bech32m address)
-};
-
-// The matches of a scan in hand-over order, kept as the BLOCKS they arrive in (the worker threads' per-batch results, moved in whole): a
-// permissive pattern yields millions, and copying them into one growing vector — reallocations and first-touch page faults, all on the
-// scanning thread — was a third of such a scan even after the records had shrunk to 96 bytes (profiles/r04_permissive.txt).
-class MatchList {
-public:
-    size_t size() const { return n_; }
-    bool empty() const { return n_ == 0; }
-    void push_back(const LiteMatch &m) {
-        if (blocks_.empty() || blocks_.back().size() == blocks_.back().capacity()) {
-            blocks_.emplace_back();
-            blocks_.back().reserve(1024);
-        }
-        blocks_.back().push_back(m);
-        n_++;
-    }
-    // the first k entries of v, without copying them
-    void take(std::vector<LiteMatch> &&v, size_t k) {
-        if (k == 0) return;
-        if (k < v.size()) v.resize(k);
-        n_ += v.size();
-        blocks_.push_back(std::move(v));
-    }
-    void append_copy(const std::vector<LiteMatch> &v) {
-        if (v.empty()) return;
-        n_ += v.size();
-        blocks_.push_back(v);
-    }
-    void append(MatchList &&o) {
-        for (auto &b : o.blocks_) {
-            n_ += b.size();
-            blocks_.push_back(std::move(b));
-        }
-        o.blocks_.clear();
-        o.n_ = 0;
-    }
-    void truncate(size_t n) {   // keep the first n
-        while (n_ > n) {
-            auto &b = blocks_.back();
-            const size_t drop = std::min(n_ - n, b.size());
-            b.resize(b.size() - drop);
-            n_ -= drop;
-            if (b.empty()) blocks_.pop_back();
-        }
-    }
-    std::vector<LiteMatch> flatten() const {
-        std::vector<LiteMatch> out;
-        out.reserve(n_);
-        for (auto &b : blocks_) out.insert(out.end(), b.begin(), b.end());
-        return out;
-    }
-    const std::vector<std::vector<LiteMatch>> &blocks() const { return blocks_; }
-
-private:
-    std::vector<std::vector<LiteMatch>> blocks_;
-    size_t n_ = 0;
-};
-
-bool make_match(const vgen_filter &flt, uint32_t format, const BatchKeys &bk, uint32_t index,
-                const uint8_t *payload, const Scalar *end, LiteMatch &g, uint32_t batch = 0, uint32_t images = 1) {
-    std::string addr = address_from_payload(format, payload);
-    if (addr.empty() || addr.size() >= sizeof g.address || !filter_accepts(flt, addr, payload)) return false;   // pattern.matches, gpu.rs:1069
-    Scalar k;
-    const uint32_t variant = images > 1 ? index / batch : 0;
-    if (images > 1) index %= batch;
-    if (bk.random) {
-        uint8_t rk[32];
-        if (!random_key_be(bk.seed, bk.stream, bk.first_index + index, rk)) return false;   // not a valid draw: no key
-        scalar_from_be(k, rk);
-    } else if (scalar_add_u64(k, bk.start, index) || !scalar_is_valid(k)) {
-        return false;                                                   // increment_key -> None
-    }
-    if (variant) {
-        Scalar kv;
-        scalar_variant(kv, k, variant);
-        k = kv;
-    }
-    if (end && scalar_cmp(k, *end) > 0) return false;                   // gpu.rs:1074-1078
-    scalar_to_be(k, g.key);
-    memcpy(g.address, addr.c_str(), addr.size() + 1);
-    return true;
-}
-
-// GeneratedAddress (src/address.rs:63-72) of a match: address, WIF (src/gpu.rs:1080-1088), hex, format, key.
-void render_match(uint32_t format, const LiteMatch &m, vgen_generated &g) {
-    memset(&g, 0, sizeof g);
-    const std::string wif = key_to_wif(format, m.key), hex = hex_lower(m.key, 32);
-    strncpy(g.address, m.address, sizeof g.address - 1);
-    strncpy(g.wif, wif.c_str(), sizeof g.wif - 1);
-    strncpy(g.hex, hex.c_str(), sizeof g.hex - 1);
-    g.format = format;
-    memcpy(g.key, m.key, 32);
-}
-
-// a recorded match (checkpoint file: keys only) back into the loop's form
-bool lite_from_key(uint32_t format, const uint8_t kb[32], LiteMatch &g) {
-    uint8_t payload[32];
-    if (!payload_from_key(format, kb, payload)) return false;
-    const std::string addr = address_from_payload(format, payload);
-    if (addr.empty() || addr.size() >= sizeof g.address) return false;
-    memcpy(g.key, kb, 32);
-    memcpy(g.address, addr.c_str(), addr.size() + 1);
-    return true;
-}
-
-// The per-pattern bookkeeping of a pattern-list scan (vgen_scan_list).  Shards hand in the confirmed matches of every batch
-// they commit, keyed by the batch's GLOBAL number (batch * shards + shard); the ledger applies them in that order — what
-// vgen_scan's order is on one context — so that "the first per_pattern keys of the walk that satisfy pattern i" does not
-// depend on which context finished first.  A match is taken when it satisfies a pattern that still wants matches; it then
-// counts toward every pattern it satisfies.
-struct ListLedger {
-    const vgen_filter *flt = nullptr;
-    uint64_t per_pattern = 0, count = UINT64_MAX;
-    uint32_t shards = 1;
-    std::vector<uint64_t> recorded;       // per shard: batches a resumed checkpoint already holds (applied up front)
-    std::mutex mu;
-    std::vector<uint64_t> got;            // matches taken per pattern
-    uint64_t unsatisfied = 0;             // patterns below per_pattern (per_pattern > 0)
-    std::map<uint64_t, std::vector<LiteMatch>> pending;   // committed batches waiting for the ones before them
-    uint64_t next = 0;                    // global batch applied next
-    std::vector<LiteMatch> accepted;
-    std::atomic<bool> done{false};
-    std::atomic<uint64_t> n_accepted{0};
-    bool arrival = false;                 // contexts that walk from bases of their own (VGEN_FLAG_ENDO): no global order to keep
-
-    void init(const vgen_filter *f, uint64_t pp, uint64_t cnt, uint32_t n_shards) {
-        flt = f;
-        per_pattern = pp;
-        count = cnt;
-        shards = std::max(1u, n_shards);
-        got.assign(f->list->patterns.size(), 0);
-        unsatisfied = pp ? got.size() : 0;
-        recorded.assign(shards, 0);
-        done = count == 0;
-    }
-    // (under mu)
-    void apply(const std::vector<LiteMatch> &v) {
-        std::vector<uint32_t> which;
-        for (const LiteMatch &m : v) {
-            if (done) return;
-            filter_which(*flt, m.address, nullptr, which);
-            bool want = per_pattern == 0 && !which.empty();
-            for (uint32_t i : which) want = want || got[i] < per_pattern;
-            if (!want) continue;
-            for (uint32_t i : which)
-                if (++got[i] == per_pattern && per_pattern) unsatisfied--;
-            accepted.push_back(m);
-            n_accepted.store(accepted.size(), std::memory_order_relaxed);
-            if (accepted.size() >= count || (per_pattern && unsatisfied == 0)) done = true;
-        }
-    }
-    bool is_recorded(uint64_t g) const { return g / shards < recorded[g % shards]; }
-    void submit(uint64_t g, std::vector<LiteMatch> &&v) {
-        std::lock_guard<std::mutex> lk(mu);
-        if (arrival) {
-            apply(v);
-            return;
-        }
-        pending[g] = std::move(v);
-        for (;;) {
-            auto it = pending.find(next);
-            if (it != pending.end()) {
-                apply(it->second);
-                pending.erase(it);
-            } else if (!is_recorded(next)) {
-                break;
-            }
-            next++;
-        }
-    }
-    // the scan is over: batches still waiting behind a gap (a failed context's that nobody took over) in their order
-    void flush() {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &kv : pending) apply(kv.second);
-        pending.clear();
-    }
-};
-
-// Threads for host-side work (candidate confirmation, rendering): the cores this process may really use — affinity mask,
-// capped by a cgroup-v2 CPU quota —, not the machine's thread count (a 256-thread host with a 16-core quota ran 256 workers).
-unsigned host_threads() {
-    unsigned n = std::thread::hardware_concurrency();
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof set, &set) == 0) n = std::min<unsigned>(n ? n : 1024, (unsigned)CPU_COUNT(&set));
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-        char quota[32];
-        long period = 0;
-        if (fscanf(f, "%31s %ld", quota, &period) == 2 && strcmp(quota, "max") != 0 && period > 0)
-            n = std::min<unsigned>(n, (unsigned)std::max(1L, atol(quota) / period));
-        fclose(f);
-    }
-    return std::max(1u, std::min(n, 64u));
-}
-
-// Checkpoint of one scan (the reference has none): which batches of every shard are
-// finished, and the matches found in them, so that an interrupted range / seeded scan resumes where it
-// stopped instead of from its first key.  A batch is committed — its matches appended and its shard's
-// counter advanced — under one lock, so every file written is a consistent prefix of the scan.  Shards
-// process their batches in dispatch order, so "batches done" is a single number per shard.
-//
-// File (text, mode 0600 — it holds the private keys of the matches; rewritten atomically through <path>.tmp,
-// fsync, rename):
-//   vgen-hip checkpoint v1 / pattern_hex= / case_insensitive= / format= / batch_size= / n_shards= /
-//   first_shard= / base= / end= / operations= / done=<per slot> / complete= / mode=range|random-seed24 / match=<key hex> ...
-struct Checkpoint {
-    std::string path;
-    std::string pattern;
-    int ci = 0;
-    uint32_t format = 0, batch = 0, n_shards = 1, first_shard = 0;
-    uint8_t base[32] = {0}, end[32] = {0};
-    bool has_end = false;
-    bool random = false;                   // a random-key scan: `base` holds its 24-byte seed (bytes 8..31), done[] counts batches of the streams
-    double interval_s = 10.0;
-
-    std::mutex mu;
-    std::vector<uint64_t> done;            // per slot (slot = shard - first_shard)
-    std::vector<LiteMatch> ledger;         // matches of committed batches, commit order
-    uint64_t operations = 0;               // over all runs
-    uint64_t resumed_operations = 0;       // as loaded
-    bool complete = false;
-    std::chrono::steady_clock::time_point last_write = std::chrono::steady_clock::now();
-    std::string error;
-
-    static std::string hex(const uint8_t *p, size_t n) { return hex_lower(p, n); }
-    static bool unhex(const std::string &s, std::vector<uint8_t> &out) {
-        if (s.size() % 2) return false;
-        out.clear();
-        for (size_t i = 0; i < s.size(); i += 2) {
-            unsigned v;
-            if (!isxdigit((unsigned char)s[i]) || !isxdigit((unsigned char)s[i + 1]) || sscanf(s.c_str() + i, "%2x", &v) != 1)
-                return false;
-            out.push_back((uint8_t)v);
-        }
-        return true;
-    }
-
-    // Loads `path` when it exists and checks that it describes this very scan.  `pin_base`: the caller
-    // fixed the base key (config.start or a seed); otherwise the file's base key is adopted.
-    // returns 1 = resumed, 0 = no file (fresh scan), -1 = error (see `error`).
-    int load(bool pin_base) {
-        FILE *f = fopen(path.c_str(), "r");
-        if (!f) return 0;
-        std::vector<std::pair<std::string, std::string>> kv;
-        char line[4096];
-        bool header = false;
-        while (fgets(line, sizeof line, f)) {
-            std::string s(line);
-            while (!s.empty() && (s.back() == '\n' || s.back() == '\r')) s.pop_back();
-            if (!header) {
-                if (s != "vgen-hip checkpoint v1") break;
-                header = true;
-                continue;
-            }
-            size_t eq = s.find('=');
-            if (eq != std::string::npos) kv.emplace_back(s.substr(0, eq), s.substr(eq + 1));
-        }
-        fclose(f);
-        if (!header) return bad("not a vgen-hip checkpoint file");
-        auto get = [&](const char *k) -> const std::string * {
-            for (auto &e : kv)
-                if (e.first == k) return &e.second;
-            return nullptr;
-        };
-        auto differs = [&](const char *k, const std::string &want) {
-            const std::string *v = get(k);
-            return !v || *v != want;
-        };
-        if (differs("pattern_hex", hex((const uint8_t *)pattern.data(), pattern.size()))) return bad("pattern");
-        if (differs("case_insensitive", std::to_string(ci))) return bad("case_insensitive");
-        if (differs("format", std::to_string(format))) return bad("format");
-        if (differs("batch_size", std::to_string(batch))) return bad("batch_size");
-        if (differs("n_shards", std::to_string(n_shards))) return bad("n_shards");
-        if (differs("first_shard", std::to_string(first_shard))) return bad("first_shard");
-        if (differs("end", has_end ? hex(end, 32) : "none")) return bad("end");
-        {
-            const std::string *m = get("mode");   // (files written before the field existed are key-range scans')
-            // ("random" without the suffix: a file of round 3's 64-bit-seeded stream function, which no longer exists)
-            if ((m ? *m : std::string("range")) != (random ? "random-seed24" : "range")) return bad("mode");
-        }
-        std::vector<uint8_t> b;
-        const std::string *bs = get("base");
-        if (!bs || !unhex(*bs, b) || b.size() != 32) return bad("base");
-        if (pin_base && memcmp(b.data(), base, 32) != 0) return bad("base");
-        memcpy(base, b.data(), 32);
-        const std::string *d = get("done"), *o = get("operations"), *c = get("complete");
-        if (!d || !o || !c) return bad("done/operations/complete");
-        std::vector<uint64_t> dn;
-        const char *p = d->c_str();
-        while (*p) {
-            char *e;
-            dn.push_back(strtoull(p, &e, 10));
-            if (e == p) return bad("done");
-            p = e;
-            while (*p == ' ') p++;
-        }
-        if (dn.size() != done.size()) return bad("done (slot count)");
-        done = dn;
-        operations = resumed_operations = strtoull(o->c_str(), nullptr, 10);
-        complete = *c == "1";
-        for (auto &e : kv) {
-            if (e.first != "match") continue;
-            LiteMatch g;
-            if (!unhex(e.second, b) || b.size() != 32 || !lite_from_key(format, b.data(), g)) return bad("match");
-            ledger.push_back(g);
-        }
-        return 1;
-    }
-    int bad(const char *field) {
-        error = "checkpoint file '" + path + "' does not belong to this scan (" + field + ")";
-        return -1;
-    }
-
-    // caller holds mu.  The file lists private keys (match=...): it is created 0600, never through a symlink,
-    // and reaches the disk (fsync) before it replaces the previous checkpoint.
-    bool write_locked() {
-        const std::string tmp = path + ".tmp";
-        const int fd = open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC | O_NOFOLLOW | O_CLOEXEC, 0600);
-        if (fd < 0) return false;
-        (void)fchmod(fd, 0600);   // an older .tmp may have been left with wider permissions
-        FILE *f = fdopen(fd, "w");
-        if (!f) {
-            close(fd);
-            return false;
-        }
-        fprintf(f, "vgen-hip checkpoint v1\npattern_hex=%s\ncase_insensitive=%d\nformat=%u\nbatch_size=%u\nn_shards=%u\n"
-                   "first_shard=%u\nbase=%s\nend=%s\noperations=%llu\ndone=",
-                hex((const uint8_t *)pattern.data(), pattern.size()).c_str(), ci, format, batch, n_shards, first_shard,
-                hex(base, 32).c_str(), has_end ? hex(end, 32).c_str() : "none", (unsigned long long)operations);
-        for (size_t i = 0; i < done.size(); i++) fprintf(f, "%s%llu", i ? " " : "", (unsigned long long)done[i]);
-        fprintf(f, "\ncomplete=%d\nmode=%s\n", complete ? 1 : 0, random ? "random-seed24" : "range");
-        for (auto &g : ledger) fprintf(f, "match=%s\n", hex(g.key, 32).c_str());
-        bool ok = fflush(f) == 0 && fsync(fd) == 0;
-        ok = (fclose(f) == 0) && ok;
-        ok = ok && rename(tmp.c_str(), path.c_str()) == 0;
-        last_write = std::chrono::steady_clock::now();
-        return ok;
-    }
-
-    // One finished batch of `slot`: its matches and the shard's counter move together.
-    void commit(uint32_t slot, const std::vector<LiteMatch> &batch_matches, uint64_t ops) {
-        std::lock_guard<std::mutex> g(mu);
-        ledger.insert(ledger.end(), batch_matches.begin(), batch_matches.end());
-        done[slot]++;
-        operations += ops;
-        if (std::chrono::duration<double>(std::chrono::steady_clock::now() - last_write).count() >= interval_s)
-            (void)write_locked();
-    }
-};
-
-// Host-side filtering of full dumps (the reference's rayon par_iter over every hash of a batch,
-// src/gpu.rs:1030-1093): a pool of worker threads that lives as long as the scan, handed one index range per
-// thread and batch.
-class HostFilterPool {
-public:
-    explicit HostFilterPool(unsigned n) : n_(std::max(1u, n)) {
-        for (unsigned t = 0; t < n_; t++) th_.emplace_back([this, t]() { loop(t); });
-    }
-    ~HostFilterPool() {
-        {
-            std::lock_guard<std::mutex> g(mu_);
-            quit_ = true;
-            gen_++;
-        }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    unsigned size() const { return n_; }
-    // runs fn(t) on every worker t and returns when all are done
-    void run(const std::function<void(unsigned)> &fn) {
-        std::unique_lock<std::mutex> g(mu_);
-        fn_ = &fn;
-        pending_ = n_;
-        gen_++;
-        cv_.notify_all();
-        done_.wait(g, [this]() { return pending_ == 0; });
-        fn_ = nullptr;
-    }
-
-private:
-    void loop(unsigned t) {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void(unsigned)> *fn;
-            {
-                std::unique_lock<std::mutex> g(mu_);
-                cv_.wait(g, [&]() { return gen_ != seen; });
-                seen = gen_;
-                if (quit_) return;
-                fn = fn_;
-            }
-            (*fn)(t);
-            {
-                std::lock_guard<std::mutex> g(mu_);
-                if (--pending_ == 0) done_.notify_all();
-            }
-        }
-    }
-    unsigned n_;
-    std::vector<std::thread> th_;
-    std::mutex mu_;
-    std::condition_variable cv_, done_;
-    const std::function<void(unsigned)> *fn_ = nullptr;
-    unsigned pending_ = 0;
-    uint64_t gen_ = 0;
-    bool quit_ = false;
-};
 
 }  // namespace
 }  // namespace vg
@@ -539,16 +108,137 @@ struct SlotProgress {
     std::atomic<uint64_t> done{0};
 };
 
-// One shard of a scan on one context.  `shared_found` (optional) is the match counter shared by the
-// shards of a multi-device scan; without it the shard counts its own matches.  `ck` (optional): the
-// scan's checkpoint; this shard is its slot `ck_slot`, skips the batches already recorded there and
-// commits each batch it finishes.  `slot` (optional): the slot's progress — the first slot->done batches are skipped
-// (another context committed them before it failed) and every batch committed here is counted in.
-// *range_done: the shard stopped because its range ran out.
-int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cfg, vgen_progress_cb cb, void *user,
-               const volatile int32_t *stop, std::atomic<uint64_t> *shared_found, std::atomic<uint64_t> *shared_ops,
-               MatchList &matches, uint64_t &total_ops, Checkpoint *ck = nullptr, uint32_t ck_slot = 0,
-               bool *range_done = nullptr, SlotProgress *slot = nullptr, const RndSeed *scan_seed = nullptr, ListLedger *ll = nullptr) {
+// Where the confirmed matches of one shard go, and with that how much of a batch has to be examined.  Three policies, by
+// the optional parts that are set:
+//   plain count (neither `ck` nor `ll`): matches are taken while `count` has room — the shard's own count, or the counter the
+//       shards of a multi-device scan share — and dropped after that; a batch is examined only as far as there is room.
+//   checkpoint (`ck`, this shard being its slot `ck_slot`): every candidate of a batch is examined and the batch is committed with
+//       ALL of its matches, also those beyond `count`: the file stays a consistent prefix of the scan whatever count a later run asks for.
+//   list ledger (`ll`): every candidate is examined and the ledger decides, in global batch order, which matches are results.
+// `slot` (optional): the slot's progress, for a context that takes the slot over after this one failed.
+struct ResultSink {
+    explicit ResultSink(uint64_t count_, std::atomic<uint64_t> *shared_found_ = nullptr) : count(count_), shared_found(shared_found_) {}
+
+    MatchList matches;                   // what this shard took (a checkpointed vgen_scan starts with the earlier runs' matches)
+    Checkpoint *ck = nullptr;
+    uint32_t ck_slot = 0;
+    SlotProgress *slot = nullptr;
+    ListLedger *ll = nullptr;
+
+    // does every candidate of a batch have to be examined?
+    bool examine_all() const { return ck != nullptr || ll != nullptr; }
+    uint64_t found() const {
+        if (ll) return ll->n_accepted.load(std::memory_order_relaxed);
+        return shared_found ? shared_found->load(std::memory_order_relaxed) : matches.size();
+    }
+    // matches `count` still has room for
+    uint64_t room() const {
+        const uint64_t have = found();
+        return have < count ? count - have : 0;
+    }
+    // is there a reason to examine another candidate of the batch in hand?
+    bool wants_more() const { return examine_all() || room() > 0; }
+    // the scan has what it was asked for (a pattern-list scan: when its ledger says so — every pattern has its matches, or `count`)
+    bool done() const { return ll ? ll->done.load(std::memory_order_relaxed) : found() >= count; }
+    // batches of this slot that are finished already: recorded in the checkpoint, or committed by the context that owned
+    // the slot before it failed; and those of them that count against max_batches (the slot's budget; a checkpoint's is per call)
+    uint64_t batches_done() const { return ck ? ck->done[ck_slot] : slot ? slot->done.load() : 0; }
+    uint64_t batches_taken_over() const { return slot && !ck ? slot->done.load() : 0; }
+
+    // A confirmed match: into the result while `count` has room (a list's results are the ledger's business), and into the
+    // batch's record when there is one.
+    void add(const LiteMatch &g) {
+        if (examine_all()) batch.push_back(g);
+        if (ll || room() == 0) return;
+        matches.push_back(g);
+        taken_uncommitted++;
+        if (shared_found) shared_found->fetch_add(1, std::memory_order_relaxed);
+    }
+    // The workers' confirmed matches of one batch (index order: part 0, part 1, ...), handed over in bulk.  Returns true when
+    // some were dropped.
+    bool add_parts(std::vector<std::vector<LiteMatch>> &part) {
+        size_t total = 0;
+        for (auto &p : part) total += p.size();
+        size_t take = ll ? 0 : (size_t)std::min<uint64_t>(total, room());
+        const size_t taken = take;
+        for (auto &p : part) {
+            if (examine_all()) batch.insert(batch.end(), p.begin(), p.end());
+            const size_t k = std::min(take, p.size());
+            matches.take(std::move(p), k);     // the worker's vector itself becomes a block of the result: nothing is copied
+            take -= k;
+        }
+        taken_uncommitted += taken;
+        if (shared_found && taken) shared_found->fetch_add(taken, std::memory_order_relaxed);
+        return taken < total && !examine_all();
+    }
+    // The batch in hand is finished: global batch `batch_no` of the scan, `tested` keys.
+    void commit(uint64_t batch_no, uint64_t tested) {
+        if (ck) ck->commit(ck_slot, batch, tested);
+        if (ll) ll->submit(batch_no, std::move(batch));
+        batch.clear();
+        if (slot) slot->done.fetch_add(1);
+        taken_uncommitted = 0;
+    }
+    // A scan that fails between examining a batch and committing it (in dump mode the host filter runs BEFORE the frame is
+    // dispatched again, and that dispatch is where a dead device shows) must not keep that batch's matches: the batch is not
+    // counted as done, so whoever resumes or takes over the slot will produce them again.
+    void rollback() {
+        matches.truncate(matches.size() - (size_t)taken_uncommitted);
+        if (shared_found) shared_found->fetch_sub(taken_uncommitted, std::memory_order_relaxed);
+        taken_uncommitted = 0;
+    }
+
+private:
+    uint64_t count;
+    std::atomic<uint64_t> *shared_found;
+    std::vector<LiteMatch> batch;                // checkpoint / list: every confirmed match of the batch in hand (the commit unit)
+    uint64_t taken_uncommitted = 0;              // matches taken from the batch in hand, not yet committed
+};
+
+// What one shard is asked to do, and what it reports back.
+struct ScanJob {
+    const vgen_scan_config *cfg = nullptr;
+    vgen_progress_cb cb = nullptr;
+    void *user = nullptr;
+    const volatile int32_t *stop = nullptr;
+    std::atomic<uint64_t> *shared_ops = nullptr;   // multi-device: the wrapper's callback adds each batch to it, so `cb` gets the batch's keys
+    const RndSeed *scan_seed = nullptr;            // random keys: the seed of the whole scan when the caller resolved one
+    uint64_t operations = 0;                       // out: keys tested by this call
+    bool range_done = false;                       // out: the shard stopped because its range ran out
+};
+
+// The candidates of one dispatch as the confirmation pass sees them — the payloads of a dump (candidate i is key index i)
+// or the records of the match ring — with what turns one into a match.
+struct Candidates {
+    const vgen_filter &flt;
+    uint32_t format;
+    const BatchKeys &keys;
+    const Scalar *end;
+    uint32_t batch, images;
+    const uint8_t *dump;        // payload of index i at dump + i * stride, or
+    size_t stride;
+    const vgen_match *recs;     // records (index, payload)
+
+    // Confirms candidates lo .. hi-1 in order, as long as more() says so, and hands every match to take().  Returns the
+    // first candidate it did not examine.
+    template <class More, class Take>
+    uint32_t confirm(uint32_t lo, uint32_t hi, More more, Take take) const {
+        LiteMatch g;
+        for (; lo < hi && more(); lo++) {
+            const bool ok = recs ? make_match(flt, format, keys, recs[lo].index, recs[lo].payload, end, g, batch, images)
+                                 : make_match(flt, format, keys, lo, dump + (size_t)lo * stride, end, g, batch, images);
+            if (ok) take(g);
+        }
+        return lo;
+    }
+    void confirm_into(uint32_t lo, uint32_t hi, std::vector<LiteMatch> &out) const {
+        confirm(lo, hi, []() { return true; }, [&out](const LiteMatch &g) { out.push_back(g); });
+    }
+};
+
+// One shard of a scan on one context: what to scan in `job`, where the matches go in `sink`.
+int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &sink) {
+    const vgen_scan_config *cfg = job.cfg;
     if (cfg->format != ctx->format) return ctx->fail(VGEN_E_INVALID, "scan format differs from the context's format");
     const bool random_keys = (cfg->flags & VGEN_SCAN_RANDOM_KEYS) != 0;
     if (ctx->endo && !random_keys && (cfg->has_start || cfg->has_end || cfg->seed || cfg->n_shards > 1 || cfg->checkpoint_path))
@@ -558,7 +248,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     //  shards keep their meaning there, they name streams of candidates, not ranges)
     if (random_keys && (cfg->has_start || cfg->has_end))
         return ctx->fail(VGEN_E_INVALID, "VGEN_SCAN_RANDOM_KEYS draws an independent key per candidate: no start / end");
-    if (random_keys && ck && !scan_seed) return ctx->fail(VGEN_E_INVALID, "a checkpointed random-key scan needs its seed (open_checkpoint sets it)");
+    if (random_keys && sink.ck && !job.scan_seed) return ctx->fail(VGEN_E_INVALID, "a checkpointed random-key scan needs its seed (open_checkpoint sets it)");
 
     const uint32_t N = ctx->batch;
     const size_t pbytes = (size_t)ctx->payload_words * 4;
@@ -622,7 +312,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     // independent random keys: candidate index = batch number x N within stream `shard` of the seed
     // (the seed of the whole scan when the caller resolved one — all shards of a multi-device scan and a resumed checkpoint
     //  share it —, else this call's own)
-    const RndSeed rnd_seed = !random_keys ? RndSeed{} : scan_seed ? *scan_seed : scan_rnd_seed(cfg->seed);
+    const RndSeed rnd_seed = !random_keys ? RndSeed{} : job.scan_seed ? *job.scan_seed : scan_rnd_seed(cfg->seed);
     Scalar current;
     if (random_keys) {
         memset(&current, 0, sizeof current);
@@ -647,8 +337,8 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     const uint64_t stride = (uint64_t)shards * N;
     // resume / take-over: this shard's first `skipped` batches are already in the checkpoint, or were committed by the
     // context that owned the slot before it failed
-    const uint64_t skipped = ck ? ck->done[ck_slot] : slot ? slot->done.load() : 0;
-    const uint64_t taken_over = slot && !ck ? skipped : 0;   // counts against max_batches: the slot's budget, not the context's
+    const uint64_t skipped = sink.batches_done();
+    const uint64_t taken_over = sink.batches_taken_over();   // counts against max_batches: the slot's budget, not the context's
     if (skipped && !exhausted && !random_keys) {
         uint64_t skip = skipped;
         while (skip && !exhausted) {
@@ -659,61 +349,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     }
 
     uint64_t dispatched = 0;
-    total_ops = 0;
-    const uint64_t count = cfg->count;
-    auto found = [&]() -> uint64_t {
-        if (ll) return ll->n_accepted.load(std::memory_order_relaxed);
-        return shared_found ? shared_found->load(std::memory_order_relaxed) : matches.size();
-    };
-    // a pattern-list scan ends when its ledger says so (every pattern has its matches, or `count`)
-    auto scan_done = [&]() -> bool { return ll ? ll->done.load(std::memory_order_relaxed) : found() >= count; };
-    std::vector<LiteMatch> batch_matches;        // matches of the batch being processed (checkpoint commit unit)
-    std::vector<LiteMatch> batch_list;           // pattern lists: every confirmed match of the batch, for the ledger
-    // A confirmed match: into the result while `count` is not reached; with a checkpoint ALWAYS into the batch's
-    // ledger entry, so that a committed batch is recorded with all of its matches and a later run with a larger
-    // count loses none.  Returns false when the match was dropped (no checkpoint, count reached).
-    uint64_t taken_uncommitted = 0;   // matches taken from the batch in hand, not yet committed (rolled back if the scan fails first)
-    auto push = [&](const LiteMatch &g) -> bool {
-        if (ll) {   // the ledger decides, in global batch order, when the batch is committed
-            batch_list.push_back(g);
-            if (ck) batch_matches.push_back(g);
-            return true;
-        }
-        const bool take = found() < count;
-        if (take) {
-            matches.push_back(g);
-            taken_uncommitted++;
-            if (shared_found) shared_found->fetch_add(1, std::memory_order_relaxed);
-        }
-        if (ck) batch_matches.push_back(g);
-        return take || ck;
-    };
-    // The workers' confirmed matches of one batch (index order: part 0, part 1, ...), handed over in bulk: as many as `count`
-    // still has room for, all of them into the checkpoint's batch record.  Returns true when some were dropped.
-    auto push_parts = [&](std::vector<std::vector<LiteMatch>> &part) -> bool {
-        if (ll) {
-            for (auto &p : part) {
-                if (ck) batch_matches.insert(batch_matches.end(), p.begin(), p.end());
-                batch_list.insert(batch_list.end(), p.begin(), p.end());
-            }
-            return false;
-        }
-        size_t total = 0;
-        for (auto &p : part) total += p.size();
-        const uint64_t have = found();
-        const uint64_t room = have < count ? count - have : 0;
-        size_t take = (size_t)std::min<uint64_t>(total, room);
-        const size_t taken = take;
-        for (auto &p : part) {
-            if (ck) batch_matches.insert(batch_matches.end(), p.begin(), p.end());
-            const size_t k = std::min(take, p.size());
-            matches.take(std::move(p), k);     // the worker's vector itself becomes a block of the result: nothing is copied
-            take -= k;
-        }
-        taken_uncommitted += taken;
-        if (shared_found && taken) shared_found->fetch_add(taken, std::memory_order_relaxed);
-        return taken < total && !ck;
-    };
+    uint64_t total_ops = 0;
     // frames this scan drives: all of them, or — filtering full dumps on the host — those that have a dump buffer
     // (runtime.cpp: ensure_dump_slab bounds the pinned memory; the host filter is the bottleneck there anyway)
     uint32_t nf = ctx->frames;
@@ -723,7 +359,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     int status = VGEN_OK;
 
     // (the host's stop flag is written by another thread: an atomic read, src/gpu.rs:980-984 reads its AtomicBool Relaxed)
-    auto stopped = [&]() { return stop && __atomic_load_n(const_cast<const int32_t *>(stop), __ATOMIC_RELAXED) != 0; };
+    auto stopped = [&]() { return job.stop && __atomic_load_n(const_cast<const int32_t *>(job.stop), __ATOMIC_RELAXED) != 0; };
     auto in_range = [&]() { return !exhausted && (!end || scalar_cmp(current, *end) <= 0); };
     auto can_dispatch = [&]() { return in_range() && (!cfg->max_batches || dispatched + taken_over < cfg->max_batches); };
     auto dispatch = [&](uint32_t frame) -> int {
@@ -780,7 +416,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     const bool table_path = random_keys || ctx->format == VGF_P2TR;
     const auto scan_t0 = std::chrono::steady_clock::now();
     bool upgrade_asked = false;
-    auto may_launch = [&]() { return can_dispatch() && !stopped() && !scan_done(); };
+    auto may_launch = [&]() { return can_dispatch() && !stopped() && !sink.done(); };
     // (a frame's stream — a hardware queue of its own — is created at its first dispatch and takes ~8 ms: a fresh context
     // starts on frame 0 alone, so that an easy pattern's first match does not wait for a second queue it never needs)
     auto prime = [&]() {
@@ -825,17 +461,14 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
             // reached; what is left unexamined counts as cut.  With a checkpoint the whole batch is examined (a committed
             // batch is recorded with every match it holds).
             const uint32_t total = (uint32_t)tested;   // N, or 6 N for an endomorphism dispatch
+            const Candidates cand{flt, cfg->format, batch_start, end, N, images, dump, pbytes, nullptr};
             uint32_t pos = 0;
-            for (unsigned round = 0; pos < total && (ck || ll || found() < count); round++) {
-                const uint64_t have = found();
-                const uint64_t need = ck || ll ? total : have < count ? count - have : 0;
+            for (unsigned round = 0; pos < total && sink.wants_more(); round++) {
+                const uint64_t need = sink.examine_all() ? total : sink.room();
                 uint64_t len = total - pos;
-                if (!ck && !ll && need < total / 8) len = std::min<uint64_t>(len, std::max<uint64_t>(need * 4, 64) << std::min(2 * round, 24u));
+                if (!sink.examine_all() && need < total / 8) len = std::min<uint64_t>(len, std::max<uint64_t>(need * 4, 64) << std::min(2 * round, 24u));
                 if (len < 1024) {
-                    LiteMatch g;
-                    const uint32_t stop_at = pos + (uint32_t)len;
-                    for (; pos < stop_at && (ck || ll || found() < count); pos++)
-                        if (make_match(flt, cfg->format, batch_start, pos, dump + (size_t)pos * pbytes, end, g, N, images)) (void)push(g);
+                    pos = cand.confirm(pos, pos + (uint32_t)len, [&]() { return sink.wants_more(); }, [&](const LiteMatch &g) { sink.add(g); });
                     continue;
                 }
                 if (!pool) pool.reset(new HostFilterPool(host_threads()));
@@ -843,12 +476,9 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
                 std::vector<std::vector<LiteMatch>> part(nt);
                 const uint32_t base = pos, span = (uint32_t)len;
                 pool->run([&](unsigned t) {
-                    const uint32_t lo = base + (uint32_t)((uint64_t)span * t / nt), hi = base + (uint32_t)((uint64_t)span * (t + 1) / nt);
-                    LiteMatch g;
-                    for (uint32_t i = lo; i < hi; i++)
-                        if (make_match(flt, cfg->format, batch_start, i, dump + (size_t)i * pbytes, end, g, N, images)) part[t].push_back(g);
+                    cand.confirm_into(base + (uint32_t)((uint64_t)span * t / nt), base + (uint32_t)((uint64_t)span * (t + 1) / nt), part[t]);
                 });
-                if (push_parts(part)) cut = true;
+                if (sink.add_parts(part)) cut = true;
                 pos += span;
             }
             if (pos < total) cut = true;   // keys left unexamined (conservative: they may not all be matches)
@@ -896,42 +526,30 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
                 prime();
                 continue;
             }
-            LiteMatch g;
-            uint32_t i = 0;
+            const Candidates cand{flt, cfg->format, batch_start, end, N, images, nullptr, 0, recs.data()};
             if (n_found >= 2048) {
                 // many candidates (a permissive pattern on a grown ring): confirm them on the worker pool, in index order
                 if (!pool) pool.reset(new HostFilterPool(host_threads()));
                 const unsigned nt = pool->size();
                 std::vector<std::vector<LiteMatch>> part(nt);
                 PROF(prof_pool, pool->run([&](unsigned t) {
-                    const uint32_t lo = (uint32_t)((uint64_t)n_found * t / nt), hi = (uint32_t)((uint64_t)n_found * (t + 1) / nt);
-                    LiteMatch gg;
-                    for (uint32_t k = lo; k < hi; k++)
-                        if (make_match(flt, cfg->format, batch_start, recs[k].index, recs[k].payload, end, gg, N, images)) part[t].push_back(gg);
+                    cand.confirm_into((uint32_t)((uint64_t)n_found * t / nt), (uint32_t)((uint64_t)n_found * (t + 1) / nt), part[t]);
                 }));
-                PROF(prof_merge, if (push_parts(part)) cut = true;);
+                PROF(prof_merge, if (sink.add_parts(part)) cut = true;);
 #ifdef VGEN_SCAN_PROFILE
                 prof_cand += n_found;
 #endif
             } else {
-                for (; i < n_found && (ck || ll || found() < count); i++)
-                    if (make_match(flt, cfg->format, batch_start, recs[i].index, recs[i].payload, end, g, N, images)) (void)push(g);
-                cut = i < n_found;   // candidates left unexamined (conservative: they may not all be matches)
+                // candidates left unexamined count as cut (conservative: they may not all be matches)
+                cut = cand.confirm(0, n_found, [&]() { return sink.wants_more(); }, [&](const LiteMatch &g) { sink.add(g); }) < n_found;
             }
         }
 
         total_ops += tested;                         // gpu.rs:1106 (batch_size; six times that for an endomorphism dispatch)
-        // With a checkpoint a batch is committed with every match it holds (push above), also those beyond
-        // `count`: the file stays a consistent prefix of the scan whatever count a later run asks for.
         cut_any = cut_any || cut;
-        if (ck) ck->commit(ck_slot, batch_matches, tested);
-        if (ll) ll->submit(batch_start.batch_no * shards + shard, std::move(batch_list));
-        batch_list.clear();
-        if (slot) slot->done.fetch_add(1);
-        taken_uncommitted = 0;
-        batch_matches.clear();
-        if (cb) cb(shared_ops ? tested : total_ops, user);   // multi-device: the wrapper adds N to the shared count under its lock
-        if (scan_done() && !dispatched_next) break;   // gpu.rs:1111
+        sink.commit(batch_start.batch_no * shards + shard, tested);
+        if (job.cb) job.cb(job.shared_ops ? tested : total_ops, job.user);   // multi-device: the wrapper adds N to the shared count under its lock
+        if (sink.done() && !dispatched_next) break;   // gpu.rs:1111
         if (table_path && !upgrade_asked && std::chrono::duration<double>(std::chrono::steady_clock::now() - scan_t0).count() >= 5.0) {
             rt_prefer_table_bits(ctx, 29, cfg->table_bits_max);   // taken into use when it is complete; nothing waits
             upgrade_asked = true;
@@ -944,20 +562,15 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, const vgen_scan_config *cf
     }
 #ifdef VGEN_SCAN_PROFILE
     fprintf(stderr, "[scan profile] wait %.3f s  pool %.3f s  merge %.3f s  dispatch %.3f s  candidates %llu  matches %zu  ops %llu\n", prof_wait, prof_pool,
-            prof_merge, prof_dispatch, (unsigned long long)prof_cand, matches.size(), (unsigned long long)total_ops);
+            prof_merge, prof_dispatch, (unsigned long long)prof_cand, sink.matches.size(), (unsigned long long)total_ops);
 #endif
-    // A scan that fails between examining a batch and committing it (in dump mode the host filter runs BEFORE the frame is
-    // dispatched again, and that dispatch is where a dead device shows) must not keep that batch's matches: the batch is not
-    // counted as done, so whoever resumes or takes over the slot will produce them again.
-    if (status != VGEN_OK && taken_uncommitted) {
-        matches.truncate(matches.size() - (size_t)taken_uncommitted);
-        if (shared_found) shared_found->fetch_sub(taken_uncommitted, std::memory_order_relaxed);
-    }
+    if (status != VGEN_OK) sink.rollback();   // the batch in hand was not committed
     // drain anything still in flight (the reference drops its runner; we must not leave frames busy)
     const bool all_processed = order.empty() && !cut_any;   // no dispatched batch was left unread or cut short
     for (uint32_t f = 0; f < ctx->frames; f++)
         if (ctx->fr[f].in_flight) (void)vgen_wait(ctx, f, nullptr, 0, nullptr, nullptr);
-    if (range_done) *range_done = status == VGEN_OK && !in_range() && all_processed;
+    job.operations = total_ops;
+    job.range_done = status == VGEN_OK && !in_range() && all_processed;
     return status;
 }
 
@@ -1046,12 +659,6 @@ int finish_result(vgen_ctx *ctx, uint32_t format, const MatchList &matches, uint
     return VGEN_OK;
 }
 
-int finish_result(vgen_ctx *ctx, uint32_t format, std::vector<LiteMatch> &matches, uint64_t ops, double secs, vgen_scan_result *out) {
-    MatchList l;
-    l.take(std::move(matches), matches.size());
-    return finish_result(ctx, format, l, ops, secs, out);
-}
-
 }  // namespace
 
 // ABI 4's vgen_scan_config, or ABI 3's 136 bytes (no table_bits_max: no cap): -> the full structure, fields beyond the caller's zero.
@@ -1066,64 +673,55 @@ static bool normalise_scan_config(const vgen_scan_config *in, vgen_scan_config &
 
 extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_config *cfg_in, vgen_progress_cb cb,
                          void *user, const volatile int32_t *stop, vgen_scan_result *out) {
-    vgen_scan_config cfg_full;
-    if (!ctx || !pattern || !out || !normalise_scan_config(cfg_in, cfg_full)) return VGEN_E_INVALID;
-    const vgen_scan_config *cfg = &cfg_full;
+    vgen_scan_config c;   // (a checkpoint may give it the file's base key)
+    if (!ctx || !pattern || !out || !normalise_scan_config(cfg_in, c)) return VGEN_E_INVALID;
     memset(out, 0, sizeof *out);
     const auto t0 = std::chrono::steady_clock::now();
     vgen_filter flt;
     std::string err;
-    if (!filter_compile(pattern, cfg->case_insensitive != 0, cfg->format, flt, err))
+    if (!filter_compile(pattern, c.case_insensitive != 0, c.format, flt, err))
         return ctx->fail(VGEN_E_PATTERN, err);
-    MatchList matches;
-    uint64_t ops = 0;
-    bool range_done = false;
-    if (!cfg->checkpoint_path) {
-        int rc = scan_shard(ctx, flt, cfg, cb, user, stop, nullptr, nullptr, matches, ops, nullptr, 0, &range_done);
-        if (rc != VGEN_OK) {
-            // the error, AND what the batches finished before it had found (complete = 0): a host that falls back to
-            // another backend (the reference's run_search does, src/lib.rs:727-746,1185-1198) keeps those matches
-            const std::string why = ctx->err;
-            (void)finish_result(ctx, cfg->format, matches, ops, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
-            out->failed_shards = 1;
-            ctx->err = why;
-            return rc;
-        }
-        out->complete = range_done;
-        return finish_result(ctx, cfg->format, matches, ops, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
-    }
-    vgen_scan_config c = *cfg;
-    Checkpoint ck;
-    const uint32_t shards = c.n_shards > 1 ? c.n_shards : 1;
+    // One flow, with or without a checkpoint.  With one, what earlier runs found counts towards `count` (committed batches keep
+    // all their matches), and nothing is dispatched when the file says the scan is complete or already holds `count` matches.
+    // While the shard runs, its matches stay the first `count` of the checkpoint's record: they serve every way out.
+    std::unique_ptr<Checkpoint> ck;
     RndSeed rnd_seed{};
-    int rc = open_checkpoint(ctx, ck, pattern, c, ctx->batch, shards, c.n_shards > 1 ? c.shard : 0, 1, rnd_seed);
-    if (rc != VGEN_OK) return rc;
-    matches.append_copy(ck.ledger);   // what earlier runs found counts towards `count` (committed batches keep all their matches)
-    if (matches.size() > c.count) matches.truncate((size_t)c.count);
-    if (!ck.complete && matches.size() < c.count)
-        rc = scan_shard(ctx, flt, &c, cb, user, stop, nullptr, nullptr, matches, ops, &ck, 0, &range_done, nullptr, &rnd_seed);
-    {
-        std::lock_guard<std::mutex> g(ck.mu);
-        ck.complete = ck.complete || (rc == VGEN_OK && range_done);
-        if (!ck.write_locked() && rc == VGEN_OK) rc = ctx->fail(VGEN_E_INVALID, "cannot write checkpoint file '" + ck.path + "'");
+    ResultSink sink(c.count);
+    if (c.checkpoint_path) {
+        ck.reset(new Checkpoint);
+        const uint32_t shards = c.n_shards > 1 ? c.n_shards : 1;
+        int rc = open_checkpoint(ctx, *ck, pattern, c, ctx->batch, shards, c.n_shards > 1 ? c.shard : 0, 1, rnd_seed);
+        if (rc != VGEN_OK) return rc;
+        sink.ck = ck.get();
+        sink.matches.append_copy(ck->ledger);
+        if (sink.matches.size() > c.count) sink.matches.truncate((size_t)c.count);
     }
+    ScanJob job;
+    job.cfg = &c;
+    job.cb = cb;
+    job.user = user;
+    job.stop = stop;
+    job.scan_seed = ck ? &rnd_seed : nullptr;
+    int rc = VGEN_OK;
+    if (!ck || (!ck->complete && sink.matches.size() < c.count)) rc = scan_shard(ctx, flt, job, sink);
+    if (ck) {
+        std::lock_guard<std::mutex> g(ck->mu);
+        ck->complete = ck->complete || (rc == VGEN_OK && job.range_done);
+        if (!ck->write_locked() && rc == VGEN_OK) rc = ctx->fail(VGEN_E_INVALID, "cannot write checkpoint file '" + ck->path + "'");
+        out->resumed_operations = ck->resumed_operations;
+    }
+    // On an error: the error, AND what the batches finished before it had found (complete = 0; with a checkpoint, earlier
+    // runs included — the file holds the same): a host that falls back to another backend (the reference's run_search does,
+    // src/lib.rs:727-746,1185-1198) keeps those matches
+    const std::string why = ctx->err;
+    const int frc = finish_result(ctx, c.format, sink.matches, job.operations, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
     if (rc != VGEN_OK) {
-        const std::string why = ctx->err;
-        std::vector<LiteMatch> all;
-        {
-            std::lock_guard<std::mutex> g(ck.mu);
-            all = ck.ledger;   // every batch committed before the failure, earlier runs included (the file holds the same)
-        }
-        if (all.size() > c.count) all.resize((size_t)c.count);
-        (void)finish_result(ctx, cfg->format, all, ops, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
-        out->resumed_operations = ck.resumed_operations;
         out->failed_shards = 1;
         ctx->err = why;
         return rc;
     }
-    out->complete = ck.complete;
-    out->resumed_operations = ck.resumed_operations;
-    return finish_result(ctx, cfg->format, matches, ops, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
+    out->complete = ck ? ck->complete : job.range_done;
+    return frc;
 }
 
 // Multi-device scan: one host thread per context, batches striped over the contexts (context i takes
@@ -1208,14 +806,22 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
                 vgen_scan_config c = base;
                 c.shard = own_bases ? 0 : slot;
                 c.n_shards = own_bases ? 0 : n_ctx;
-                bool rd = false;
-                MatchList got;
-                uint64_t o = 0;
-                const int rc = scan_shard(ctxs[i], flt, &c, cb ? (vgen_progress_cb)locked_cb : nullptr, &cbc, stop, &found, &ops_shared,
-                                          got, o, ckp, slot, &rd, own_bases ? nullptr : &progress[slot], random_keys ? &rnd_seed : nullptr, ll);
+                ScanJob job;
+                job.cfg = &c;
+                job.cb = cb ? (vgen_progress_cb)locked_cb : nullptr;
+                job.user = &cbc;
+                job.stop = stop;
+                job.shared_ops = &ops_shared;
+                job.scan_seed = random_keys ? &rnd_seed : nullptr;
+                ResultSink sink(c.count, &found);
+                sink.ck = ckp;
+                sink.ck_slot = slot;
+                sink.slot = own_bases ? nullptr : &progress[slot];
+                sink.ll = ll;
+                const int rc = scan_shard(ctxs[i], flt, job, sink);
                 std::unique_lock<std::mutex> lk(q_mu);
-                part[slot].append(std::move(got));
-                ops[slot] += o;
+                part[slot].append(std::move(sink.matches));
+                ops[slot] += job.operations;
                 if (rc != VGEN_OK) {
                     // this context retires; the slot it was working on is up for adoption (never for endomorphism contexts:
                     // they walk from random bases of their own, there is no range to complete)
@@ -1226,7 +832,7 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
                     q_cv.notify_all();
                     return;
                 }
-                range_done[slot] = rd;
+                range_done[slot] = job.range_done;
                 slot_finished[slot] = 1;
                 // finished a slot: adopt an orphan if the scan still wants keys, else wait while anybody may still fail
                 running--;
@@ -1265,25 +871,27 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
     }
     out->complete = ckp ? ck.complete : all_done;
     out->failed_shards = (int32_t)failed_ctx;
+    // The results: a list's are its ledger's, in the scan's order; else what the checkpoint recorded (earlier runs' matches +
+    // every batch committed by this one) or what the shards took, in ascending key order
     std::vector<LiteMatch> all;
-    uint64_t total = 0;
-    if (ckp && !ll) all = ck.ledger;   // earlier runs' matches + every batch committed by this one
-    for (uint32_t i = 0; i < n_ctx; i++) {
-        if (!ckp && !ll) {
-            const std::vector<LiteMatch> flat = part[i].flatten();
-            all.insert(all.end(), flat.begin(), flat.end());
-        }
-        total += ops[i];
-    }
-    if (ll) {   // the ledger's matches, in the scan's order
+    if (ll) {
         ll->flush();
         all = ll->accepted;
+    } else if (ckp) {
+        all = ck.ledger;
     } else {
-        std::sort(all.begin(), all.end(), [](const LiteMatch &a, const LiteMatch &b) { return memcmp(a.key, b.key, 32) < 0; });
+        for (auto &p : part) {
+            const std::vector<LiteMatch> flat = p.flatten();
+            all.insert(all.end(), flat.begin(), flat.end());
+        }
     }
-    if (all.size() > cfg->count) all.resize((size_t)cfg->count);
+    if (!ll) std::sort(all.begin(), all.end(), [](const LiteMatch &a, const LiteMatch &b) { return memcmp(a.key, b.key, 32) < 0; });
+    uint64_t total = 0;
+    for (uint64_t o : ops) total += o;
+    MatchList result;
+    result.take(std::move(all), (size_t)std::min<uint64_t>(all.size(), cfg->count));
     const std::string why = first_err != VGEN_OK ? ctxs[first_err_ctx]->err : std::string();
-    const int frc = finish_result(ctxs[0], cfg->format, all, total, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
+    const int frc = finish_result(ctxs[0], cfg->format, result, total, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
     if (first_err != VGEN_OK && !absorbed) {
         out->complete = 0;
         ctxs[first_err_ctx]->err = why;
@@ -1294,14 +902,20 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
     return frc;
 }
 
+// The arguments vgen_scan_multi and vgen_scan_list share: contexts of one batch size, a configuration, a result to fill (zeroed here).
+static bool multi_args(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_scan_config *cfg_in, vgen_scan_config &full, vgen_scan_result *out) {
+    if (!ctxs || n_ctx == 0 || !out || !normalise_scan_config(cfg_in, full)) return false;
+    for (uint32_t i = 0; i < n_ctx; i++)
+        if (!ctxs[i] || ctxs[i]->batch != ctxs[0]->batch) return false;
+    memset(out, 0, sizeof *out);
+    return true;
+}
+
 extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const vgen_scan_config *cfg_in,
                                vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out) {
     vgen_scan_config cfg_full;
-    if (!ctxs || n_ctx == 0 || !pattern || !out || !normalise_scan_config(cfg_in, cfg_full)) return VGEN_E_INVALID;
+    if (!pattern || !multi_args(ctxs, n_ctx, cfg_in, cfg_full, out)) return VGEN_E_INVALID;
     const vgen_scan_config *cfg = &cfg_full;
-    for (uint32_t i = 0; i < n_ctx; i++)
-        if (!ctxs[i] || ctxs[i]->batch != ctxs[0]->batch) return VGEN_E_INVALID;
-    memset(out, 0, sizeof *out);
     vgen_filter flt;
     std::string err;
     if (!filter_compile(pattern, cfg->case_insensitive != 0, cfg->format, flt, err))
@@ -1315,10 +929,7 @@ extern "C" int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter
                               const vgen_scan_config *cfg_in, vgen_progress_cb cb, void *user, const volatile int32_t *stop,
                               vgen_scan_result *out) {
     vgen_scan_config cfg_full;
-    if (!ctxs || n_ctx == 0 || !list || !out || !normalise_scan_config(cfg_in, cfg_full)) return VGEN_E_INVALID;
-    for (uint32_t i = 0; i < n_ctx; i++)
-        if (!ctxs[i] || ctxs[i]->batch != ctxs[0]->batch) return VGEN_E_INVALID;
-    memset(out, 0, sizeof *out);
+    if (!list || !multi_args(ctxs, n_ctx, cfg_in, cfg_full, out)) return VGEN_E_INVALID;
     if (!list->list) return ctxs[0]->fail(VGEN_E_INVALID, "vgen_scan_list needs a pattern list (vgen_filter_compile_list)");
     if (cfg_full.format != list->format) return ctxs[0]->fail(VGEN_E_INVALID, "scan format differs from the pattern list's format");
     cfg_full.case_insensitive = list->case_insensitive ? 1 : 0;   // the list carries it
