@@ -432,3 +432,21 @@ int core_mul_signed(int st, const unsigned char *key_be, unsigned char *xy) {
 }
 }
 
+#include "../../vgen_amd/csrc/core/ptab_eval.h"
+
+extern "C" {
+// Host twin of ptab_lookup_kernel's search: ptab_find (core/ptab_eval.h, the source the list kernel inlines) of every x[i] in
+// the table given as plain arrays (device_types.h: DevPtab).  tests/test_ptab_tables.py checks the synthetic tables of the
+// GPU harness (tests/native/list_dev.hip) against it before any of them reaches a device.
+void core_ptab_find(u32 bits, u32 n, const u32 *bitmap, const u32 *offsets, const u64 *lo, const u64 *hi, const u64 *x,
+                    int count, int *out) {
+    DevPtab t;
+    t.bitmap = bitmap;
+    t.offsets = offsets;
+    t.lo = lo;
+    t.hi = hi;
+    t.bits = bits;
+    t.n = n;
+    for (int i = 0; i < count; i++) out[i] = ptab_find(t, x[i]);
+}
+}

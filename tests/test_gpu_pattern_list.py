@@ -1,7 +1,9 @@
 """Pattern lists on the MI355X: every dispatch path of a list filter (device kind 5: the per-key kernels in dump mode into a
 device-only buffer, then ptab_lookup_kernel + ptab_compact_kernel) reports a superset of the oracle's matches whose confirmed
 part is exactly the oracle's, and vgen_scan_list returns the first keys of the walk per pattern, across contexts and
-checkpoints."""
+checkpoints.  Hits land here where the hashes put them; the kernel-level edges (interval bounds, word / thread / wave / pass
+boundaries of the compaction, a full ring, a wrapping count, ragged counts over stale buffers) are in
+tests/test_gpu_list_kernels.py."""
 import os
 import random
 
