@@ -201,6 +201,33 @@ int core_filter_ntests(const char *pattern, int ci, unsigned format) {
     if (!filter_compile(pattern, ci != 0, format, f, err)) return -1;
     return (int)f.dev.count;
 }
+// The compiled device tests themselves, for the Python model of tests/match_vectors.py and its range-bound vectors.
+// hdr: kind, flags, count, witver, whether the filter carries chk_lut, dfa_bytes.  tests: 18 words per test (a[8], b[8],
+// chk_mask, chk_value), DEVF_MAX_TESTS of them.  -1 on pattern error.
+int core_filter_tests(const char *pattern, int ci, unsigned format, u32 *hdr, u32 *tests) {
+    vgen_filter f;
+    std::string err;
+    if (!filter_compile(pattern, ci != 0, format, f, err)) return -1;
+    hdr[0] = f.dev.kind;
+    hdr[1] = f.dev.flags;
+    hdr[2] = f.dev.count;
+    hdr[3] = f.dev.witver;
+    hdr[4] = f.dev.chk_lut && !f.chk_lut.empty() ? 1u : 0u;
+    hdr[5] = f.dev.dfa_bytes;
+    const bool has_tests = f.dev.kind == DEVF_RANGES || f.dev.kind == DEVF_MASKED;
+    for (u32 t = 0; t < DEVF_MAX_TESTS; t++) {
+        const DevFilterTest &T = f.dev.tests[t];
+        u32 *o = tests + 18 * t;
+        const bool live = has_tests && t < f.dev.count;
+        for (int i = 0; i < DEVF_WORDS; i++) {
+            o[i] = live ? T.a[i] : 0u;
+            o[8 + i] = live ? T.b[i] : 0u;
+        }
+        o[16] = live ? T.chk_mask : 0u;
+        o[17] = live ? T.chk_value : 0u;
+    }
+    return 0;
+}
 int core_regex_match(const char *pattern, int ci, const char *text) {
     Dfa d;
     std::string err;
@@ -306,6 +333,10 @@ int core_dfa_check(const char *pattern, int ci, unsigned format, const unsigned 
     }
     return (int)DEVF_DFA;
 }
+}
+
+extern "C" {
+void core_divmod_d5(u32 hi, u32 lo, u32 *q, u32 *r) { divmod_d5(hi, lo, *q, *r); }
 }
 
 #include "../../vgen_amd/csrc/core/taproot.h"
