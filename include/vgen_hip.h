@@ -53,10 +53,15 @@ typedef enum vgen_format {
     VGEN_FMT_P2TR = 3,
     VGEN_FMT_P2PKH_UNCOMPRESSED = 4,
     VGEN_FMT_ETHEREUM = 5,
-    VGEN_FMT_ETHEREUM_CONTRACT = 6   /* not a format of the reference: the address of the contract the key's account creates with its FIRST
+    VGEN_FMT_ETHEREUM_CONTRACT = 6,  /* not a format of the reference: the address of the contract the key's account creates with its FIRST
                                         transaction (CREATE, nonce 0): C = keccak256(0xd6 0x94 || A || 0x80)[12..32] with A the Ethereum
                                         address of the key.  Payload, address string and key rendering as for VGEN_FMT_ETHEREUM; the key
                                         controls the deployer A, not C.  Other nonces: vgen_contract_address. */
+    VGEN_FMT_ETHEREUM_CREATE2 = 7    /* not a format of the reference: the CREATE2 (EIP-1014) address
+                                        keccak256(0xff || deployer || salt || keccak256(init_code))[12..32], searched by SALT (see "CREATE2"
+                                        below).  No key owns such an address: vgen_derive is VGEN_E_UNSUPPORTED and the key-walking
+                                        dispatches and scans refuse the format; vgen_set_create2 / vgen_dispatch_create2 / vgen_scan_create2
+                                        drive it.  Payload, address string, filters and difficulty as for VGEN_FMT_ETHEREUM. */
 } vgen_format;
 
 /* Parameters of vgen_create; replaces the arguments of GpuRunner::new(batch_size, backend)
@@ -350,6 +355,30 @@ int vgen_derive(uint32_t format, const uint8_t key_be[32], char *address, size_t
  * 0x80 + length and the big-endian bytes).  nonce 0 is what VGEN_FMT_ETHEREUM_CONTRACT searches on the device. */
 int vgen_contract_address(const uint8_t deployer[20], uint64_t nonce, uint8_t out[20]);
 
+/* Keccak-256 (the pre-SHA-3 padding Ethereum uses) of `len` bytes, any length: e.g. the init_code_hash of a CREATE2 search. */
+int vgen_keccak256(const uint8_t *data, size_t len, uint8_t out[32]);
+
+/* ---- CREATE2 (EIP-1014): vanity contract addresses by salt ------------------------------------------------
+ * address = keccak256(0xff || deployer[20] || salt[32] || init_code_hash[32])[12..32]: the contract that the factory `deployer`
+ * creates when it executes CREATE2 with exactly this salt and exactly this init code (init_code_hash = keccak256(init_code)).
+ * A search is described by the job (deployer, init_code_hash, salt_prefix[24]): candidate `counter` is the salt
+ * salt_prefix || u64be(counter) - salt bytes 0..23 are the caller's (e.g. msg.sender and four bytes of the caller's choosing),
+ * bytes 24..31 hold the counter big-endian.  The device runs one Keccak block per salt and no curve arithmetic.
+ * (The job travels as three byte arrays, not as a structure: the set of structures of this header is closed under ABI 4.) */
+int vgen_create2_address(const uint8_t deployer[20], const uint8_t salt[32], const uint8_t init_code_hash[32], uint8_t out[20]);
+/* salt = salt_prefix || u64be(counter). */
+int vgen_create2_salt(const uint8_t salt_prefix[24], uint64_t counter, uint8_t salt[32]);
+/* The job of a VGEN_FMT_ETHEREUM_CREATE2 context (VGEN_E_INVALID on any other); only while nothing is in flight (VGEN_E_STATE).
+ * Such a context holds the frames' streams, match rings and, from their first use, the dump or list buffers - none of the
+ * point-arithmetic scratch and no table (vgen_get_memory shows it); VGEN_FLAG_ENDO at vgen_create is VGEN_E_UNSUPPORTED. */
+int vgen_set_create2(vgen_ctx *ctx, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]);
+/* Tests counters first_counter + i, i < batch_size, on `frame`; vgen_wait, vgen_read_dump / vgen_dump_view, vgen_set_filter (single
+ * patterns and lists), vgen_set_match_cap and the frame timers work as for any format: a record's index is i, keys_tested is
+ * batch_size.  VGEN_E_STATE without a job; VGEN_E_RANGE when first_counter + batch_size - 1 passes 2^64 - 1 (nothing is enqueued).
+ * Known limitation: pattern lists and on-device automata (device kind 4) inherit the dump's rule that an all-zero payload is never a
+ * candidate, so the all-zero address (probability 2^-160) is not reported by them. */
+int vgen_dispatch_create2(vgen_ctx *ctx, uint32_t frame, uint64_t first_counter);
+
 /* ---- provider patterns (src/provider.rs) -------------------------------------------------------------- */
 
 /* provider::resolve (src/provider.rs:12-52): "boha:b1000:66" / "boha:b1000/66" -> the puzzle's target
@@ -473,6 +502,17 @@ int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const 
 int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter *list, uint64_t per_pattern,
                    const vgen_scan_config *cfg, vgen_progress_cb cb, void *user, const volatile int32_t *stop,
                    vgen_scan_result *out);
+/* A CREATE2 salt search over one or several VGEN_FMT_ETHEREUM_CREATE2 contexts (same batch_size): global batch b covers counters
+ * first_counter + b * batch_size .. and goes to context b mod n_ctx; device candidates are confirmed on the host with the exact
+ * automaton (a pattern without a device filter is filtered on the host from dumps); results come in ascending counter order,
+ * truncated to cfg->count; operations count batch_size per finished batch.  From cfg: format (must be 7), count, case_insensitive,
+ * max_batches (per context); a set has_start, has_end, seed, shard, n_shards > 1, checkpoint_path or flags is VGEN_E_UNSUPPORTED.
+ * complete = 1 when the 64-bit counter space ran out.  The job is installed on every context (vgen_set_create2).
+ * In a result: address = the EIP-55 address, key = the 32-byte SALT, hex = wif = "0x" + the salt in lowercase hex, format = 7.
+ * Not provided for this format: checkpoints / resuming, pattern-list scans, take-over of a failed context's stripe. */
+int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const uint8_t deployer[20], const uint8_t init_code_hash[32],
+                      const uint8_t salt_prefix[24], uint64_t first_counter, const vgen_scan_config *cfg, vgen_progress_cb cb, void *user,
+                      const volatile int32_t *stop, vgen_scan_result *out);
 void vgen_scan_result_free(vgen_scan_result *r);
 
 #ifdef __cplusplus

@@ -49,6 +49,7 @@ class AddressFormat(enum.IntEnum):
     P2pkhUncompressed = 4
     Ethereum = 5
     EthereumContract = 6   # VGEN_FMT_ETHEREUM_CONTRACT: the contract the key's account creates with nonce 0 (not in the reference)
+    EthereumCreate2 = 7    # VGEN_FMT_ETHEREUM_CREATE2: a CREATE2 (EIP-1014) address searched by salt (not in the reference)
 
     def charset_name(self) -> str:
         """AddressFormat::charset_name (src/address.rs:39-45)."""
@@ -145,6 +146,14 @@ _L.vgen_key_add.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
 _L.vgen_derive.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
                            ctypes.c_size_t]
 _L.vgen_contract_address.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
+_L.vgen_keccak256.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
+_L.vgen_create2_address.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+_L.vgen_create2_salt.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
+_L.vgen_set_create2.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
+_L.vgen_dispatch_create2.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]
+_L.vgen_scan_create2.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                 ctypes.c_uint64, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
+                                 ctypes.POINTER(_ScanResult)]
 _L.vgen_device_name.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
 _L.vgen_scan.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p,
                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_ScanResult)]
@@ -242,6 +251,56 @@ def contract_address(deployer, nonce=0) -> bytes:
     out = ctypes.create_string_buffer(20)
     _check(_L.vgen_contract_address(bytes(deployer), nonce, out))
     return out.raw
+
+
+def _hexbytes(v, n, what):
+    if isinstance(v, str):
+        v = bytes.fromhex(v[2:] if v[:2] in ("0x", "0X") else v)
+    v = bytes(v)
+    if len(v) != n:
+        raise ValueError("%s is %d bytes" % (what, n))
+    return v
+
+
+def keccak256(data) -> bytes:
+    """vgen_keccak256: Keccak-256 (Ethereum's, pre-SHA-3 padding) of any number of bytes."""
+    data = bytes(data)
+    out = ctypes.create_string_buffer(32)
+    _check(_L.vgen_keccak256(data, len(data), out))
+    return out.raw
+
+
+def create2_address(deployer, salt, init_code_hash) -> bytes:
+    """vgen_create2_address: keccak256(0xff || deployer || salt || init_code_hash)[12:] (EIP-1014); bytes or 0x-hex strings."""
+    out = ctypes.create_string_buffer(20)
+    _check(_L.vgen_create2_address(_hexbytes(deployer, 20, "deployer"), _hexbytes(salt, 32, "salt"), _hexbytes(init_code_hash, 32, "init_code_hash"), out))
+    return out.raw
+
+
+class Create2Job:
+    """What a CREATE2 salt search is about: the factory `deployer` that executes CREATE2, the hash of the init code (or the init code
+    itself) and the caller's part of the salt, `salt_prefix` (up to 24 bytes, left-aligned, zero padded).  Candidate `counter` is the
+    salt salt_prefix || counter as 8 big-endian bytes."""
+
+    def __init__(self, deployer, init_code_hash=None, init_code=None, salt_prefix=b""):
+        if (init_code_hash is None) == (init_code is None):
+            raise ValueError("give exactly one of init_code_hash and init_code")
+        self.deployer = _hexbytes(deployer, 20, "deployer")
+        self.init_code_hash = keccak256(init_code) if init_code is not None else _hexbytes(init_code_hash, 32, "init_code_hash")
+        if isinstance(salt_prefix, str):
+            salt_prefix = bytes.fromhex(salt_prefix[2:] if salt_prefix[:2] in ("0x", "0X") else salt_prefix)
+        if len(salt_prefix) > 24:
+            raise ValueError("salt_prefix is at most 24 bytes")
+        self.salt_prefix = bytes(salt_prefix).ljust(24, b"\0")
+
+    def salt(self, counter: int) -> bytes:
+        """vgen_create2_salt."""
+        out = ctypes.create_string_buffer(32)
+        _check(_L.vgen_create2_salt(self.salt_prefix, counter, out))
+        return out.raw
+
+    def address(self, counter: int) -> bytes:
+        return create2_address(self.deployer, self.salt(counter), self.init_code_hash)
 
 
 @dataclass
@@ -486,6 +545,14 @@ class GpuRunner:
         self._n_keys = n
         _check(_L.vgen_dispatch_keys(self._h, frame, blob, n), self._h)
 
+    def set_create2(self, job: "Create2Job"):
+        """vgen_set_create2: the job of an EthereumCreate2 runner."""
+        _check(_L.vgen_set_create2(self._h, job.deployer, job.init_code_hash, job.salt_prefix), self._h)
+
+    def dispatch_create2(self, first_counter: int, frame: int):
+        """vgen_dispatch_create2: salts first_counter .. first_counter + batch_size - 1 of the job; results as for dispatch()."""
+        _check(_L.vgen_dispatch_create2(self._h, frame, first_counter), self._h)
+
     def fail_after(self, dispatches: int):
         """vgen_debug_fail_after: fault injection — dispatches fail with VGEN_E_HIP once `dispatches` more were accepted.
         Exists only in the test build of the library (tests/conftest.py: hooks_api)."""
@@ -635,6 +702,32 @@ def scan_gpu_with_runner(pattern: str, config: ScanConfig, runner,
     if rc < 0:
         # a failing scan still hands over what its finished batches found (vgen_scan_result is filled, complete = 0)
         msg = _L.vgen_last_error(runner._h)
+        err = VgenError(rc, msg.decode() if msg else "")
+        err.partial = out
+        raise err
+    return out
+
+
+def scan_create2(pattern: str, job: Create2Job, config: ScanConfig, runner, first_counter: int = 0,
+                 progress_cb: Optional[Callable[[int], None]] = None, stop=None) -> ScanResult:
+    """vgen_scan_create2: the salts of `job` from counter `first_counter` on, over one EthereumCreate2 GpuRunner or a list of them.
+    In a match, `hex` (and `wif`) is "0x" + the 32-byte salt; the address exists only when job.deployer executes CREATE2 with that
+    salt and the job's init code."""
+    runners = list(runner) if isinstance(runner, (list, tuple)) else [runner]
+    c = _scan_config(config)
+    res = _ScanResult()
+    cb = _PROGRESS(lambda ops, _u: progress_cb(ops)) if progress_cb else ctypes.cast(None, _PROGRESS)
+    stop_p = ctypes.byref(stop) if stop is not None else None
+    arr = (ctypes.c_void_p * len(runners))(*[r._h for r in runners])
+    rc = _L.vgen_scan_create2(arr, len(runners), pattern.encode(), job.deployer, job.init_code_hash, job.salt_prefix, first_counter,
+                              ctypes.byref(c), cb, None, stop_p, ctypes.byref(res))
+    out = ScanResult(operations=res.operations, elapsed_secs=res.elapsed_secs, complete=bool(res.complete), failed_shards=res.failed_shards)
+    for i in range(res.n_matches):
+        g = res.matches[i]
+        out.matches.append(GeneratedAddress(g.address.decode(), g.wif.decode(), g.hex.decode(), AddressFormat(g.format)))
+    _L.vgen_scan_result_free(ctypes.byref(res))
+    if rc < 0:
+        msg = _L.vgen_last_error(runners[0]._h)
         err = VgenError(rc, msg.decode() if msg else "")
         err.partial = out
         raise err

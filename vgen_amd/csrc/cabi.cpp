@@ -10,6 +10,7 @@
 #include "host/filter.h"
 #include "host/pattern_info.h"
 #include "host/provider.h"
+#include "core/hash.h"
 #include "host/scalar.h"
 #include "runtime.h"
 
@@ -364,6 +365,40 @@ int vgen_contract_address(const uint8_t deployer[20], uint64_t nonce, uint8_t ou
     vg::host_keccak256(msg, n, h);
     memcpy(out, h + 12, 20);
     return VGEN_OK;
+}
+
+int vgen_keccak256(const uint8_t *data, size_t len, uint8_t out[32]) {
+    if ((!data && len) || !out) return VGEN_E_INVALID;
+    vg::host_keccak256(data, len, out);
+    return VGEN_OK;
+}
+
+int vgen_create2_address(const uint8_t deployer[20], const uint8_t salt[32], const uint8_t init_code_hash[32], uint8_t out[20]) {
+    if (!deployer || !salt || !init_code_hash || !out) return VGEN_E_INVALID;
+    // through the single-source twin of the device block (core/hash.h), on the 22 message words the kernel hashes
+    vg::u32 m[22], a[5];
+    vg::create2_message(deployer, salt, init_code_hash, m);
+    vg::keccak256_create2_addr(m, a);
+    memcpy(out, a, 20);
+    return VGEN_OK;
+}
+
+int vgen_create2_salt(const uint8_t salt_prefix[24], uint64_t counter, uint8_t salt[32]) {
+    if (!salt_prefix || !salt) return VGEN_E_INVALID;
+    memcpy(salt, salt_prefix, 24);
+    for (int i = 0; i < 8; i++) salt[24 + i] = (uint8_t)(counter >> (8 * (7 - i)));
+    return VGEN_OK;
+}
+
+int vgen_set_create2(vgen_ctx *ctx, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]) {
+    if (!ctx) return VGEN_E_INVALID;
+    if (!deployer || !init_code_hash || !salt_prefix) return ctx->fail(VGEN_E_INVALID, "vgen_set_create2: null job field");
+    return vg::rt_set_create2(ctx, deployer, init_code_hash, salt_prefix);
+}
+
+int vgen_dispatch_create2(vgen_ctx *ctx, uint32_t frame, uint64_t first_counter) {
+    if (!ctx) return VGEN_E_INVALID;
+    return vg::rt_dispatch_create2(ctx, frame, first_counter);
 }
 
 }  // extern "C"

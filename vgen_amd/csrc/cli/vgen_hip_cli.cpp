@@ -7,6 +7,7 @@
 // error here: this build has no CPU backend).  Added: --seed (the reference seeds from OS entropy
 // only), --devices (batch-striped multi-GPU scan), --frames, --checkpoint (resumable scans).
 #include <ctype.h>
+#include <errno.h>
 #include <signal.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -44,6 +45,10 @@ struct Opts {
     uint64_t mem_budget = 0;                  // vgen_params.device_mem_budget_bytes (0 = automatic)
     int puzzle = 0;
     long prefix_length = -1;   // -l / --prefix-length (provider patterns)
+    // -f ethereum-create2: the job of the salt search
+    std::string deployer, init_code_hash, init_code_file, salt_prefix, salt_start;
+    bool has_deployer = false, has_init_code_hash = false, has_init_code_file = false, has_salt_prefix = false, has_salt_start = false;
+    bool any_create2_option() const { return has_deployer || has_init_code_hash || has_init_code_file || has_salt_prefix || has_salt_start; }
 };
 
 [[noreturn]] void die(const std::string &msg) {
@@ -58,8 +63,9 @@ int format_id(const std::string &f) {
     if (f == "p2tr") return VGEN_FMT_P2TR;
     if (f == "ethereum") return VGEN_FMT_ETHEREUM;
     if (f == "ethereum-contract") return VGEN_FMT_ETHEREUM_CONTRACT;
+    if (f == "ethereum-create2") return VGEN_FMT_ETHEREUM_CREATE2;
     if (f == "p2pkh-uncompressed") return VGEN_FMT_P2PKH_UNCOMPRESSED;
-    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract)");
+    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2)");
 }
 
 const char *format_display(int id) {   // Display for AddressFormat, src/address.rs:48-58
@@ -70,6 +76,7 @@ const char *format_display(int id) {   // Display for AddressFormat, src/address
     case VGEN_FMT_P2SH_P2WPKH: return "P2SH-P2WPKH";
     case VGEN_FMT_P2TR: return "P2TR";
     case VGEN_FMT_ETHEREUM_CONTRACT: return "Ethereum contract (nonce 0)";   // (no comma: the csv writer keeps eight plain columns)
+    case VGEN_FMT_ETHEREUM_CREATE2: return "Ethereum contract (CREATE2)";
     default: return "Ethereum";
     }
 }
@@ -204,6 +211,10 @@ void usage() {
             "                                           the reference's CPU path, src/scanner.rs:118-169 —, six keys per draw unless\n"
             "                                           --no-endo; ~3x slower than the walk)\n"
             "                    PATTERN may be a provider pattern boha:b1000:N [-l PREFIX_LENGTH] [--provider-table CSV]\n"
+            "  vgen-hip generate -f ethereum-create2 -p PATTERN --deployer 0xADDR (--init-code-hash 0xHASH | --init-code-file FILE)\n"
+            "                    [--salt-prefix 0xHEX] [--salt-start N] [-c COUNT] [-i] [--devices ..] [-o ..]   (CREATE2, EIP-1014: searches the\n"
+            "                    SALT salt_prefix (up to 24 bytes, zero padded) || 8-byte counter from N on; the printed key is the salt, and the\n"
+            "                    address exists only when exactly this deployer runs CREATE2 with exactly this init code)\n"
             "  vgen-hip generate --patterns-file FILE [--per-pattern N] ...   (instead of -p: one start-anchored prefix per line,\n"
             "                    one scan; N results per pattern (default 1, 0 = unbounded), -c caps the total (default: none);\n"
             "                    each result's pattern field is the lowest-index line it satisfies.  range takes it too)\n"
@@ -227,7 +238,8 @@ Opts parse(int argc, char **argv) {
     static const char *const long_with_value[] = {"--pattern", "--format", "--count", "--output", "--file", "--gpu-batch-size", "--repeat",
                                                   "--seed", "--devices", "--frames", "--checkpoint", "--range", "--puzzle", "--key", "--address",
                                                   "--prefix-length", "--provider-table", "--threads", "--backend", "--cpu-batch-size", "--table-bits-max",
-                                                  "--mem-budget-gib", "--patterns-file", "--per-pattern"};
+                                                  "--mem-budget-gib", "--patterns-file", "--per-pattern", "--deployer", "--init-code-hash", "--init-code-file",
+                                                  "--salt-prefix", "--salt-start"};
     static const char short_with_value[] = "pfcorkaltT";
     std::vector<std::string> args;
     bool next_is_value = false;
@@ -297,6 +309,11 @@ Opts parse(int argc, char **argv) {
         else if (a == "--no-tui" || a == "--tui") {}                                   // no TUI in this build
         else if (a == "-l" || a == "--prefix-length") o.prefix_length = strtol(val().c_str(), nullptr, 10);
         else if (a == "--provider-table") o.provider_table = val();
+        else if (a == "--deployer") { o.deployer = val(); o.has_deployer = true; }
+        else if (a == "--init-code-hash") { o.init_code_hash = val(); o.has_init_code_hash = true; }
+        else if (a == "--init-code-file") { o.init_code_file = val(); o.has_init_code_file = true; }
+        else if (a == "--salt-prefix") { o.salt_prefix = val(); o.has_salt_prefix = true; }
+        else if (a == "--salt-start") { o.salt_start = val(); o.has_salt_start = true; }
         else if (a == "-t" || a == "--threads" || a == "--backend" || a == "--cpu-batch-size") (void)val();   // accepted, not applicable
         else if (a == "-h" || a == "--help") { usage(); exit(0); }
         else die("unexpected argument '" + a + "'");
@@ -353,7 +370,7 @@ Resolved resolve_provider(Opts &o, bool for_range) {
     vgen_provider_build_pattern(addr, o.prefix_length > 0 ? (uint32_t)o.prefix_length : 0, pat, sizeof pat);
     if (o.prefix_length > 0 || !for_range) fprintf(stderr, "Provider: %s → %s → pattern '%s'\n", o.pattern.c_str(), addr, pat);
     else fprintf(stderr, "Provider: %s → %s → exact match\n", o.pattern.c_str(), addr);
-    static const char *names[] = {"p2pkh", "p2wpkh", "p2sh-p2wpkh", "p2tr", "p2pkh-uncompressed", "ethereum", "ethereum-contract"};
+    static const char *names[] = {"p2pkh", "p2wpkh", "p2sh-p2wpkh", "p2tr", "p2pkh-uncompressed", "ethereum", "ethereum-contract", "ethereum-create2"};
     o.format = names[fmt];
     r.pattern = pat;
     r.from_provider = true;
@@ -372,6 +389,70 @@ void warn_impossible_pattern(const std::string &pattern, bool ignore_case, int f
     if (strcmp(cs, "Base58") == 0)
         fprintf(stderr, "  Base58 excludes: 0 (zero), O (uppercase o), I (uppercase i), l (lowercase L)\n");
     fprintf(stderr, "\n");
+}
+
+// -f ethereum-create2: the job of the salt search from the command line, checked before any device is opened.
+struct Create2Job {
+    uint8_t deployer[20] = {0}, init_code_hash[32] = {0}, salt_prefix[24] = {0};
+    uint64_t first = 0;
+};
+
+// "0x" + hex digits (the 0x optional) -> at most `cap` bytes; the number of bytes, or -1
+int parse_hex_bytes(const std::string &s, uint8_t *out, size_t cap) {
+    const std::string h = s.compare(0, 2, "0x") == 0 || s.compare(0, 2, "0X") == 0 ? s.substr(2) : s;
+    if (h.size() % 2 != 0 || h.size() / 2 > cap) return -1;
+    for (size_t i = 0; i < h.size(); i++)
+        if (!isxdigit((unsigned char)h[i])) return -1;
+    for (size_t i = 0; i < h.size() / 2; i++) out[i] = (uint8_t)strtoul(h.substr(2 * i, 2).c_str(), nullptr, 16);
+    return (int)(h.size() / 2);
+}
+
+Create2Job create2_job(const Opts &o, bool has_range, bool list) {
+    if (o.cmd != "generate" || has_range) die("'-f ethereum-create2' searches salts: use it with 'generate' (no key range)");
+    if (o.seed) die("the argument '--seed' cannot be used with '-f ethereum-create2' (the search walks salt counters from --salt-start)");
+    if (o.random_keys) die("the argument '--random-keys' cannot be used with '-f ethereum-create2' (there are no keys)");
+    if (!o.checkpoint.empty()) die("the argument '--checkpoint' cannot be used with '-f ethereum-create2'");
+    if (list) die("the argument '--patterns-file' cannot be used with '-f ethereum-create2'");
+    Create2Job j;
+    if (!o.has_deployer) die("the following required arguments were not provided for '-f ethereum-create2': --deployer <0xADDRESS>");
+    if (parse_hex_bytes(o.deployer, j.deployer, 20) != 20) die("--deployer must be an address of 20 bytes in hex");
+    if (o.has_init_code_hash == o.has_init_code_file) die("exactly one of '--init-code-hash' and '--init-code-file' is required for '-f ethereum-create2'");
+    if (o.has_init_code_hash) {
+        if (parse_hex_bytes(o.init_code_hash, j.init_code_hash, 32) != 32) die("--init-code-hash must be 32 bytes in hex");
+    } else {
+        FILE *f = fopen(o.init_code_file.c_str(), "rb");
+        if (!f) die("cannot read init code file '" + o.init_code_file + "'");
+        std::string code;
+        char buf[65536];
+        for (size_t n; (n = fread(buf, 1, sizeof buf, f)) > 0;) code.append(buf, n);
+        fclose(f);
+        vgen_keccak256(reinterpret_cast<const uint8_t *>(code.data()), code.size(), j.init_code_hash);   // the file's bytes as they are
+    }
+    if (o.has_salt_prefix) {
+        uint8_t pre[25];
+        const std::string h = o.salt_prefix.compare(0, 2, "0x") == 0 || o.salt_prefix.compare(0, 2, "0X") == 0 ? o.salt_prefix.substr(2) : o.salt_prefix;
+        if (h.size() > 48) die("--salt-prefix takes at most 24 bytes (the last 8 bytes of the salt are the counter)");
+        const int n = parse_hex_bytes(o.salt_prefix, pre, 24);
+        if (n < 0) die("--salt-prefix must be hex");
+        memcpy(j.salt_prefix, pre, (size_t)n);   // left-aligned, zero padded
+    }
+    if (o.has_salt_start) {
+        char *end = nullptr;
+        errno = 0;
+        j.first = strtoull(o.salt_start.c_str(), &end, 0);
+        if (errno || !end || *end || o.salt_start.empty() || o.salt_start[0] == '-') die("--salt-start must be a counter below 2^64");
+    }
+    return j;
+}
+
+std::string hex0x(const uint8_t *b, size_t n) {
+    std::string s = "0x";
+    char t[3];
+    for (size_t i = 0; i < n; i++) {
+        snprintf(t, sizeof t, "%02x", b[i]);
+        s += t;
+    }
+    return s;
 }
 
 // `estimate` (src/lib.rs:345-375): difficulty heuristic over a measured rate.  The reference times its CPU
@@ -402,12 +483,15 @@ int run_estimate(Opts &o) {
     cfg.format = (uint32_t)fmt;
     cfg.count = UINT64_MAX;
     cfg.case_insensitive = o.ignore_case;
-    cfg.seed = o.seed;
+    cfg.seed = fmt == VGEN_FMT_ETHEREUM_CREATE2 ? 0 : o.seed;
     double rate = 0;
     for (int pass = 0; pass < 2; pass++) {   // first pass warms the device up
         cfg.max_batches = pass ? 96 : 12;
         vgen_scan_result res;
-        if (vgen_scan(c, o.pattern.c_str(), &cfg, nullptr, nullptr, &g_stop, &res) != VGEN_OK) die(vgen_last_error(c));
+        const uint8_t zero[32] = {0};   // ethereum-create2: the rate does not depend on the job
+        const int rc = fmt == VGEN_FMT_ETHEREUM_CREATE2 ? vgen_scan_create2(&c, 1, o.pattern.c_str(), zero, zero, zero, 0, &cfg, nullptr, nullptr, &g_stop, &res)
+                                                        : vgen_scan(c, o.pattern.c_str(), &cfg, nullptr, nullptr, &g_stop, &res);
+        if (rc != VGEN_OK) die(vgen_last_error(c));
         rate = res.elapsed_secs > 0 ? (double)res.operations / res.elapsed_secs : 0.0;
         vgen_scan_result_free(&res);
     }
@@ -483,6 +567,11 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
     const std::string &pattern = pattern_arg;
     if (o.no_gpu) die("--no-gpu: this build has no CPU scan path (the MI355X engine is the only backend)");
     const int fmt = format_id(o.format);
+    const bool create2 = fmt == VGEN_FMT_ETHEREUM_CREATE2;
+    if (!create2 && o.any_create2_option())
+        die("'--deployer', '--init-code-hash', '--init-code-file', '--salt-prefix' and '--salt-start' belong to '-f ethereum-create2'");
+    Create2Job job;
+    if (create2) job = create2_job(o, has_range, list != nullptr);
     // surface pattern errors before touching the device (Pattern::new, pattern.rs:21-33)
     if (!list) {
         vgen_filter *probe = nullptr;
@@ -505,7 +594,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         // a vanity search proper — random base, no range, no seed, no checkpoint — may test any keys it likes:
         // six images per curve point (VGEN_FLAG_ENDO, +30 % keys per second); everything else walks k0 + i
         // (--random-keys: six keys per draw; seeds name candidate streams there, so they do not rule it out)
-        if (!o.no_endo && fmt != 3 && (o.random_keys || (!has_range && !o.seed && o.checkpoint.empty()))) p.flags |= VGEN_FLAG_ENDO;
+        if (!o.no_endo && fmt != 3 && !create2 && (o.random_keys || (!has_range && !o.seed && o.checkpoint.empty()))) p.flags |= VGEN_FLAG_ENDO;
         vgen_ctx *c = nullptr;
         if (vgen_create(&p, &c) != VGEN_OK) die(std::string("GPU initialization failed: ") + vgen_last_error(nullptr));
         ctxs.push_back(c);
@@ -544,7 +633,9 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
     for (uint64_t rep = 0; rep < (o.repeat ? o.repeat : 1) && !g_stop; rep++) {   // lib.rs:825-865
         vgen_scan_result res;
         prog.base = total_ops;
-        int rc = list ? vgen_scan_list(ctxs.data(), (uint32_t)ctxs.size(), list, o.per_pattern, &cfg, show_progress ? progress_cb : nullptr,
+        int rc = create2 ? vgen_scan_create2(ctxs.data(), (uint32_t)ctxs.size(), pattern.c_str(), job.deployer, job.init_code_hash, job.salt_prefix, job.first, &cfg,
+                                             show_progress ? progress_cb : nullptr, &prog, &g_stop, &res)
+                 : list ? vgen_scan_list(ctxs.data(), (uint32_t)ctxs.size(), list, o.per_pattern, &cfg, show_progress ? progress_cb : nullptr,
                                        &prog, &g_stop, &res)
                  : ctxs.size() == 1 ? vgen_scan(ctxs[0], pattern.c_str(), &cfg, show_progress ? progress_cb : nullptr, &prog, &g_stop, &res)
                                     : vgen_scan_multi(ctxs.data(), (uint32_t)ctxs.size(), pattern.c_str(), &cfg, show_progress ? progress_cb : nullptr,
@@ -582,11 +673,19 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         char deployer[128] = "";
         if (fmt == VGEN_FMT_ETHEREUM_CONTRACT && vgen_derive(VGEN_FMT_ETHEREUM, g.key, deployer, sizeof deployer, nullptr, 0) != VGEN_OK)
             die("malformed or out-of-range secret key");
+        // ethereum-create2: the "key" is the salt; the address exists only for this deployer and this init code
+        std::string c2_hash;
+        if (create2) {
+            snprintf(deployer, sizeof deployer, "%s", hex0x(job.deployer, 20).c_str());
+            c2_hash = hex0x(job.init_code_hash, 32);
+        }
         if (o.output == "text") {
             fprintf(w, "=== Match %zu of %zu ===\n", idx + 1, all.size());
-            fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nWIF     : %s\nHex     : %s\n", pattern.c_str(),
-                    fmt_name.c_str(), g.address, g.wif, g.hex);
-            if (deployer[0]) fprintf(w, "Deployer: %s  (the account of this key; its first transaction must create the contract)\n", deployer);
+            if (create2) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSalt    : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex);
+            else fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nWIF     : %s\nHex     : %s\n", pattern.c_str(),
+                         fmt_name.c_str(), g.address, g.wif, g.hex);
+            if (create2) fprintf(w, "Deployer: %s  (the factory that must run CREATE2 with the salt above)\nInitHash: %s\n", deployer, c2_hash.c_str());
+            else if (deployer[0]) fprintf(w, "Deployer: %s  (the account of this key; its first transaction must create the contract)\n", deployer);
             if (!o.quiet) {
                 fprintf(w, "Ops     : %s (%.0f/sec)\n", with_commas(total_ops).c_str(), rate);
                 fprintf(w, "Time    : %s\n", format_duration(total_secs).c_str());
@@ -597,6 +696,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             const char *nl = pretty ? "\n  " : "", *sp = pretty ? " " : "";
             fprintf(w, "{%s\"address\":%s%s,", nl, sp, json_str(g.address).c_str());
             if (deployer[0]) fprintf(w, "%s\"deployer\":%s%s,", nl, sp, json_str(deployer).c_str());
+            if (create2) fprintf(w, "%s\"init_code_hash\":%s%s,", nl, sp, json_str(c2_hash).c_str());
             fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
                        "\"operations\":%s%llu,%s\"elapsed_secs\":%s%s,%s\"rate\":%s%s%s}\n",
                     nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str(), nl,

@@ -420,4 +420,43 @@ VG_HD void keccak256_create_addr(const u32 acc[5], u32 out[5]) {
     out[4] = (u32)(a[3] >> 32);
 }
 
+// CREATE2 (EIP-1014): the low 20 bytes of Keccak-256(0xff || deployer[20] || salt[32] || keccak256(init_code)[32]) - 85 bytes, one
+// rate block.  m = the 22 little-endian words of the message (bytes 85..87 zero), exactly what the device block keccak_create2_block
+// takes (hashgen.py prog_keccak_create2); the 0x01 of the pre-SHA-3 padding goes to byte 85 here as there.
+VG_HD void keccak256_create2_addr(const u32 m[22], u32 out[5]) {
+    u64 a[25];
+#pragma unroll
+    for (int i = 0; i < 10; i++) a[i] = (u64)m[2 * i] | ((u64)m[2 * i + 1] << 32);
+    a[10] = (u64)m[20] | ((u64)(m[21] | 0x00000100u) << 32);
+#pragma unroll
+    for (int i = 11; i < 25; i++) a[i] = 0;
+    a[16] = 0x8000000000000000ULL;   // last byte of the 136-byte rate block
+    keccak_f1600(a);
+    out[0] = (u32)(a[1] >> 32);
+    out[1] = (u32)a[2];
+    out[2] = (u32)(a[2] >> 32);
+    out[3] = (u32)a[3];
+    out[4] = (u32)(a[3] >> 32);
+}
+
+// The 22 message words of a CREATE2 candidate from its 85 bytes (little-endian words, bytes 85..87 zero).
+VG_HD void create2_message(const uint8_t deployer[20], const uint8_t salt[32], const uint8_t init_code_hash[32], u32 m[22]) {
+    uint8_t b[88];
+    b[0] = 0xff;
+    for (int i = 0; i < 20; i++) b[1 + i] = deployer[i];
+    for (int i = 0; i < 32; i++) b[21 + i] = salt[i];
+    for (int i = 0; i < 32; i++) b[53 + i] = init_code_hash[i];
+    b[85] = b[86] = b[87] = 0;
+    for (int i = 0; i < 22; i++) m[i] = (u32)b[4 * i] | ((u32)b[4 * i + 1] << 8) | ((u32)b[4 * i + 2] << 16) | ((u32)b[4 * i + 3] << 24);
+}
+
+// The salt counter of a CREATE2 search: salt bytes 24..31 = message bytes 45..52 hold `counter` big-endian, i.e. byte 1 of word 11
+// up to byte 0 of word 13 (the counter straddles Keccak lanes 5 and 6).  m holds the message of counter 0 (those bytes zero).
+VG_HD void create2_place_counter(u32 m[22], u64 counter) {
+    const u32 lo = bswap32((u32)(counter >> 32)), hi = bswap32((u32)counter);   // message bytes 45..48 and 49..52 as little-endian words
+    m[11] |= lo << 8;
+    m[12] |= (lo >> 24) | (hi << 8);
+    m[13] |= hi >> 24;
+}
+
 }  // namespace vg

@@ -12,13 +12,17 @@ enum : int {
     VGF_P2TR = 3,
     VGF_P2PKH_UNCOMPRESSED = 4,
     VGF_ETHEREUM = 5,
-    VGF_ETHEREUM_CONTRACT = 6   // address of the contract the account deploys with nonce 0 (not a format of the reference)
+    VGF_ETHEREUM_CONTRACT = 6,  // address of the contract the account deploys with nonce 0 (not a format of the reference)
+    VGF_ETHEREUM_CREATE2 = 7    // CREATE2 (EIP-1014) address searched by salt: no key, no curve point (not a format of the reference)
 };
 
 // the two formats whose payload is (derived from) the Ethereum account address: hex strings, both coordinates hashed
 constexpr bool vgf_is_eth(int fmt) { return fmt == VGF_ETHEREUM || fmt == VGF_ETHEREUM_CONTRACT; }
 // the format whose address STRING a payload of `fmt` is written as: a contract's 20 bytes are spelled like an account's
-constexpr int vgf_string_format(int fmt) { return fmt == VGF_ETHEREUM_CONTRACT ? (int)VGF_ETHEREUM : fmt; }
+constexpr int vgf_string_format(int fmt) { return (fmt == VGF_ETHEREUM_CONTRACT || fmt == VGF_ETHEREUM_CREATE2) ? (int)VGF_ETHEREUM : fmt; }
+// the formats whose address string is "0x" + 40 hex digits with EIP-55 casing (vgf_is_eth says how the per-key kernels hash a
+// point and stays what it is: a CREATE2 address has no point behind it)
+constexpr bool vgf_is_hex(int fmt) { return vgf_string_format(fmt) == VGF_ETHEREUM; }
 
 
 // Device-side prefilter program (built by host/filter.cpp from the pattern's DFA).
@@ -107,6 +111,16 @@ struct PtabArgs {
     const uint32_t *dfa_blob;
     uint32_t dfa_bytes;
     uint32_t fmt;
+};
+
+// Arguments of create2_kernel: the message of salt counter 0 (core/hash.h keccak256_create2_addr; uniform, scalar loads from the
+// kernarg segment), the dispatch's first counter, and where the results go.  Lane i tests counter first + i.
+struct Create2Args {
+    uint32_t m[22];              // 0xff || deployer || salt_prefix || 0^8 || init_code_hash, bytes 85..87 zero
+    unsigned long long first;
+    uint32_t *payloads;          // slot i at payloads + 5 i: every slot (DUMP) or the slots of hit lanes only
+    unsigned long long *hits;    // !DUMP: the hit mask, one bit per slot (batch / 64 words)
+    const DevFilter *filter;     // !DUMP: the context's prefilter (kinds 1 - 3)
 };
 
 // Per-dispatch uniform points of the sequential kernel: Q_j = (k0 + N/2 - S/2 + j)*G and the

@@ -378,6 +378,21 @@ def prog_keccak_create(grouped=False):
     return p, "const u32 a[5]", prologue
 
 
+def prog_keccak_create2(grouped=False):
+    """CREATE2 (EIP-1014) address: the low 20 bytes of Keccak-256(0xff || deployer || salt || keccak256(init_code)), 85 bytes, one
+    rate block (core/hash.h keccak256_create2_addr).  w = the 22 words of the message, lanes 0..10: the searched salt counter sits in
+    bytes 45..52 (words 11..13), everything else is the job's.  Byte 85 - in the high word of lane 10, an input - takes the 0x01 of the
+    pre-SHA-3 padding, ORed in by the prologue; lane 16 ends the block."""
+    p = Program(grouped)
+    lanes = [(p.input(f"m{2 * i}"), p.input(f"m{2 * i + 1}")) for i in range(11)] + [(0, 0)] * 14
+    lanes[16] = (0, 0x80000000)
+    a = p.keccak_f1600(lanes)
+    p.outputs = [a[1][1], a[2][0], a[2][1], a[3][0], a[3][1]]
+    p.prune()
+    prologue = [f"u32 m{i} = w[{i}];" for i in range(21)] + ["u32 m21 = w[21] | 0x00000100u;"]
+    return p, "const u32 w[22]", prologue
+
+
 # keccak_addr_block: in round 4, in dependency order, the block ran no faster than hipcc's rolled rounds (same 5 003 instructions per key); as runs by
 # issue class with the priority changes it is worth +28 % on every Ethereum configuration (profiles/r05_keccak_ab.txt): 1 351 half-rate funnel
 # shifts against 2 844 full-rate booleans, which now ride in the second places of the issue slots.
@@ -387,7 +402,9 @@ OPTIONAL = {}    # (--with NAME: blocks generated for an A/B only)
 # the second Keccak block of VGF_ETHEREUM_CONTRACT; a table of its own, emitted after PROGRAMS
 PROGRAMS_CONTRACT = {"keccak_create_block": prog_keccak_create}
 # yields per function where they differ from the default
-YIELDS = {"keccak_addr_block": "none", "keccak_create_block": "none"}
+# the one block of VGF_ETHEREUM_CREATE2 (create2_kernel); again a table of its own, emitted after the two above
+PROGRAMS_CREATE2 = {"keccak_create2_block": prog_keccak_create2}
+YIELDS = {"keccak_addr_block": "none", "keccak_create_block": "none", "keccak_create2_block": "none"}
 
 
 # ---- the Python model of the instruction list (CPU tests) ---------------------------------------------------------------------
@@ -661,7 +678,7 @@ def add_filler(lines, mode, n):
 
 
 def function_source(name, grouped=False, yields="every:3", window=0, distance=1, prio=None, class_window=0):
-    p, params, prologue = {**PROGRAMS, **OPTIONAL, **PROGRAMS_CONTRACT}[name](grouped)
+    p, params, prologue = {**PROGRAMS, **OPTIONAL, **PROGRAMS_CONTRACT, **PROGRAMS_CREATE2}[name](grouped)
     left = spread(p, window, distance) if window else None
     runs = by_class(p, class_window, CLASS_DISTANCE) if class_window else None
     reg, nreg = allocate(p)
@@ -720,6 +737,15 @@ def generate(grouped=False, yields=DEFAULT_YIELD, window=0, distance=1, override
     return src
 
 
+def generate_create2(grouped=False, yields=DEFAULT_YIELD, window=0, distance=1, overrides=None,
+                     prio=tuple(int(x) for x in DEFAULT_PRIO.split(":")), class_window=DEFAULT_CLASS_WINDOW):
+    """The table PROGRAMS_CREATE2 under the same options: main() writes it behind generate()'s text, which stays what it was."""
+    src = ""
+    for name in PROGRAMS_CREATE2:
+        src += function_source(name, grouped, (overrides or {}).get(name, YIELDS.get(name, yields)), window, distance, prio, class_window)
+    return src
+
+
 def main(argv):
     def opt(name, default):
         return argv[argv.index(name) + 1] if name in argv else default
@@ -736,11 +762,11 @@ def main(argv):
         mode, n = opt("--filler", "").split(":")
         FILLER = (mode, int(n))
     overrides = dict(a.split("=", 1) for i, a in enumerate(argv) if i and argv[i - 1] == "--yield-for")   # --yield-for name=mode
-    sys.stdout.write(generate(opt("--order", "natural") == "grouped", opt("--yield", DEFAULT_YIELD),
-                              int(opt("--window", "0")), int(opt("--distance", "1")), overrides,
-                              [a for i, a in enumerate(argv) if i and argv[i - 1] == "--with"],
-                              None if opt("--prio", DEFAULT_PRIO) == "none" else tuple(int(x) for x in opt("--prio", DEFAULT_PRIO).split(":")),
-                              int(opt("--class-window", str(DEFAULT_CLASS_WINDOW)))))
+    grouped, yields, window, distance = opt("--order", "natural") == "grouped", opt("--yield", DEFAULT_YIELD), int(opt("--window", "0")), int(opt("--distance", "1"))
+    prio = None if opt("--prio", DEFAULT_PRIO) == "none" else tuple(int(x) for x in opt("--prio", DEFAULT_PRIO).split(":"))
+    class_window = int(opt("--class-window", str(DEFAULT_CLASS_WINDOW)))
+    sys.stdout.write(generate(grouped, yields, window, distance, overrides, [a for i, a in enumerate(argv) if i and argv[i - 1] == "--with"], prio, class_window))
+    sys.stdout.write(generate_create2(grouped, yields, window, distance, overrides, prio, class_window))
 
 
 if __name__ == "__main__":

@@ -2031,4 +2031,58 @@ hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream)
     return hipGetLastError();
 }
 
+// ---- CREATE2 (VGF_ETHEREUM_CREATE2): a search over salts --------------------------------------------------------------------
+// No curve arithmetic: candidate `counter` is the salt salt_prefix || u64be(counter), its address one Keccak rate block over the 85
+// bytes 0xff || deployer || salt || init_code_hash.  One salt per thread; the job's words are uniform (kernel arguments), only
+// words 11 - 13, which carry the counter, differ per lane.
+//   DUMP   every payload to slot i, nothing else (dump mode; pattern lists and on-device automata, whose kernels follow)
+//   !DUMP  the prefilter (kinds 1 - 3) on the five words in registers, the wave's ballot into the hit mask with one plain 64-bit
+//          store, the payload of hit lanes only; ptab_compact_kernel, which reads payloads at hit indices only, makes the records.
+// No atomics, no LDS; the match path of the per-key kernels (match_slot) is not used here.
+template <bool DUMP>
+__global__ void __launch_bounds__(256) create2_kernel(const Create2Args a) {
+#if VG_BASE_PRIO && VG_KECCAK_BLOCK
+    __builtin_amdgcn_s_setprio(VG_BASE_PRIO);   // (the level the hash block returns to)
+#endif
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    u32 m[22];
+#pragma unroll
+    for (int k = 0; k < 22; k++) m[k] = a.m[k];
+    create2_place_counter(m, a.first + i);
+    u32 pl[5];
+#if VG_KECCAK_BLOCK
+    keccak_create2_block(m, pl);
+#else
+    keccak256_create2_addr(m, pl);
+#endif
+    u32 *o = a.payloads + (size_t)i * 5;
+    if (DUMP) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) o[k] = pl[k];
+    } else {
+        const bool hit = filter_eval_n<5>(a.filter, pl);
+        const unsigned long long mask = __ballot(hit);
+        if ((threadIdx.x & 63u) == 0) a.hits[i >> 6] = mask;
+        if (hit) {
+#pragma unroll
+            for (int k = 0; k < 5; k++) o[k] = pl[k];
+        }
+    }
+}
+
+hipError_t launch_create2(const Create2Args &a, uint32_t batch, const PtabArgs *compact, hipStream_t stream) {
+    if (batch == 0 || batch % 256 != 0 || !a.payloads) return hipErrorInvalidValue;
+    if (!compact) {
+        hipLaunchKernelGGL((create2_kernel<true>), dim3(batch / 256), dim3(256), 0, stream, a);
+        return hipGetLastError();
+    }
+    if (!a.hits || !a.filter || compact->payloads != a.payloads || compact->hits != a.hits || compact->stride != batch || compact->images != 1)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((create2_kernel<false>), dim3(batch / 256), dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ptab_compact_kernel<5>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, *compact);
+    return hipGetLastError();
+}
+
 }  // namespace vg

@@ -300,6 +300,7 @@ std::string address_from_payload(uint32_t format, const uint8_t *payload) {
         return segwit_address("bc", 1, payload, 32);
     case VGF_ETHEREUM:
     case VGF_ETHEREUM_CONTRACT:
+    case VGF_ETHEREUM_CREATE2:
         return eip55_address(payload);
     default:
         return std::string();

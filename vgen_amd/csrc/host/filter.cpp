@@ -539,7 +539,8 @@ bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t 
         break;
     }
     case VGF_ETHEREUM:
-    case VGF_ETHEREUM_CONTRACT: {   // (the contract address is an address string like the account's)
+    case VGF_ETHEREUM_CONTRACT:
+    case VGF_ETHEREUM_CREATE2: {   // (a contract address is an address string like the account's)
         // EIP-55 casing depends on a second Keccak the kernel does not compute: derive the device
         // test from the case-insensitive language (a superset); the host confirms with the exact DFA.
         Dfa folded;
@@ -615,7 +616,7 @@ bool list_ranges(const std::string &pattern, bool ci, uint32_t format, uint32_t 
     Dfa d;
     std::string err;
     // Ethereum: the device sees the payload, not the EIP-55 casing: ranges of the case-folded language (the host confirms)
-    if (!regex_compile(pattern, ci || vgf_is_eth((int)format), d, err)) {
+    if (!regex_compile(pattern, ci || vgf_is_hex((int)format), d, err)) {
         why = err;
         return false;
     }
@@ -653,8 +654,8 @@ bool list_ranges(const std::string &pattern, bool ci, uint32_t format, uint32_t 
             return false;
         }
         for (auto &r : ranges) out.push_back({top64_of160(r.lo), top64_of160(r.hi), index});
-    } else if (format == VGF_P2WPKH || format == VGF_P2TR || vgf_is_eth((int)format)) {
-        const bool eth = vgf_is_eth((int)format);
+    } else if (format == VGF_P2WPKH || format == VGF_P2TR || vgf_is_hex((int)format)) {
+        const bool eth = vgf_is_hex((int)format);
         const char *head = eth ? "0x" : format == VGF_P2TR ? "bc1p" : "bc1q";
         const char *alphabet = eth ? HEXL : BECH32;
         const unsigned bits = eth ? 4 : 5, n_data = eth ? 40 : format == VGF_P2TR ? 52 : 32;
@@ -862,7 +863,7 @@ bool payload_from_address(uint32_t format, const std::string &address, uint8_t o
             if (carry) return false;
         }
         memcpy(out, v + 1, 20);
-    } else if (vgf_is_eth((int)format)) {
+    } else if (vgf_is_hex((int)format)) {
         if (a.size() != 42 || a[0] != '0' || (a[1] != 'x' && a[1] != 'X')) return false;
         for (int i = 0; i < 20; i++) {
             int hv[2];

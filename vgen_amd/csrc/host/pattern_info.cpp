@@ -19,7 +19,8 @@ Charset charset_of(unsigned format) {
     case VGF_P2WPKH:
     case VGF_P2TR: return Charset::Bech32;
     case VGF_ETHEREUM:
-    case VGF_ETHEREUM_CONTRACT: return Charset::Hex;
+    case VGF_ETHEREUM_CONTRACT:
+    case VGF_ETHEREUM_CREATE2: return Charset::Hex;
     default: return Charset::None;
     }
 }
@@ -181,7 +182,8 @@ uint64_t pattern_difficulty(const std::string &p, bool case_insensitive, unsigne
         case VGF_P2WPKH: shared = starts("bc1q") ? 4 : starts("bc1") ? 3 : starts("bc") ? 2 : starts("b"); break;
         case VGF_P2TR: shared = starts("bc1p") ? 4 : starts("bc1") ? 3 : starts("bc") ? 2 : starts("b"); break;
         case VGF_ETHEREUM:
-        case VGF_ETHEREUM_CONTRACT: shared = (starts("0x") || starts("0X")) ? 2 : starts("0"); break;
+        case VGF_ETHEREUM_CONTRACT:
+        case VGF_ETHEREUM_CREATE2: shared = (starts("0x") || starts("0X")) ? 2 : starts("0"); break;
         default: break;
         }
     }

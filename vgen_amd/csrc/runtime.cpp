@@ -11,6 +11,7 @@
 #include <functional>
 #include <mutex>
 
+#include "core/hash.h"
 #include "device/launch.h"
 #include "host/host_ec.h"
 
@@ -226,6 +227,10 @@ int rt_device_name(int device, std::string &name, std::string &err) {
     return VGEN_OK;
 }
 
+// the device side of a CREATE2 context (defined beside the other dispatches): rt_create hands them to the context
+static int create2_set(vgen_ctx *c, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]);
+static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter);
+
 int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
     // ABI 4's parameter block, or ABI 3's 28 bytes (no table_bits, no budget: both automatic)
     constexpr uint32_t PARAMS_ABI3 = 28;
@@ -251,9 +256,13 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
         err = "device index out of range";
         return VGEN_E_NODEVICE;
     }
-    if (p->format > VGF_ETHEREUM_CONTRACT) {
+    if (p->format > VGF_ETHEREUM_CREATE2) {
         err = "unknown address format";
         return VGEN_E_INVALID;
+    }
+    if (p->format == VGF_ETHEREUM_CREATE2 && (p->flags & VGEN_FLAG_ENDO)) {
+        err = "VGEN_FLAG_ENDO: a CREATE2 search has no curve points to take images of";
+        return VGEN_E_UNSUPPORTED;
     }
     const bool trace = getenv("VGEN_TRACE_CREATE") != nullptr;
     auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
@@ -324,6 +333,22 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
     // of this context's format touches is allocated here, nothing on the dispatch path.
     lap("checks + hipSetDevice");
     c->fr.resize(c->frames);
+    if (c->format == VGF_ETHEREUM_CREATE2) {
+        // a search over salts hashes no curve point: no per-frame scratch, no offset table, no generator table - the filter
+        // program and the match rings here, the dump or list buffers at their first use
+        const uint64_t fixed = sizeof(DevFilter) + (uint64_t)up256(match_bytes(c->match_cap)) * c->frames;
+        if (c->mem_budget && fixed > c->mem_budget)
+            return bail(VGEN_E_NOMEM, "device_mem_budget_bytes " + std::to_string(c->mem_budget) + " does not cover the frames: " + std::to_string(fixed) + " bytes");
+        e = hipMalloc((void **)&c->d_filter, sizeof(DevFilter));
+        if (e != hipSuccess) return bail(VGEN_E_NOMEM, std::string("hipMalloc(filter): ") + hipGetErrorString(e));
+        c->frames_bytes += sizeof(DevFilter);
+        if (int rc = rt_set_match_cap(c, c->match_cap)) return bail(rc, c->err);
+        lap("filter + match rings");
+        c->create2_set = create2_set;
+        c->create2_dispatch = create2_dispatch;
+        *out = c;
+        return VGEN_OK;
+    }
     const size_t scratch_b = up256(scratch_words(c) * sizeof(uint32_t));
     const size_t p2tr_b = up256(p2tr_words(c) * sizeof(uint32_t));
     const size_t frame_b = scratch_b + p2tr_b;
@@ -570,7 +595,14 @@ bool dump_mode(const vgen_ctx *c) { return !c->have_filter || c->h_filter.kind =
 bool list_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind == DEVF_LIST; }
 // The Ethereum-contract kernels only write payloads (kernels.hip: DumpOnly): a pattern's device filter runs behind them over
 // the frame's device-only payload buffer and the list path's compaction makes the records.
-bool deferred_filter(const vgen_ctx *c) { return c->format == VGF_ETHEREUM_CONTRACT && c->have_filter && !dump_mode(c) && !list_mode(c); }
+// CREATE2 takes the same road for an on-device automaton (create2_kernel<DUMP>, then the automaton over the written payloads) ...
+bool deferred_filter(const vgen_ctx *c) {
+    return (c->format == VGF_ETHEREUM_CONTRACT || (c->format == VGF_ETHEREUM_CREATE2 && c->h_filter.kind == DEVF_DFA)) && c->have_filter && !dump_mode(c) &&
+           !list_mode(c);
+}
+// ... and evaluates a prefilter (kinds 1 - 3) inside its own kernel: hit mask and the hits' payloads into the frame's list buffers,
+// then the compaction alone.
+bool inline_filter(const vgen_ctx *c) { return c->format == VGF_ETHEREUM_CREATE2 && c->have_filter && !dump_mode(c) && !list_mode(c) && !deferred_filter(c); }
 
 // The pattern-list buffers of every frame: the payloads of a dispatch (20 B per key, x 6 on an endomorphism context, 32 B for
 // P2TR) and the hit mask (one bit per slot).  Device memory only — the payloads never leave the device — so, unlike dump mode,
@@ -686,7 +718,7 @@ int rt_set_filter(vgen_ctx *c, const vgen_filter *f) {
     if (int rc = upload(c, c->d_filter, &c->h_filter, sizeof(DevFilter))) return rc;
     c->have_filter = true;
     if (dump_mode(c)) return ensure_dump_slab(c);
-    if (deferred_filter(c)) return ensure_list_slab(c);
+    if (deferred_filter(c) || inline_filter(c)) return ensure_list_slab(c);
     return VGEN_OK;
 }
 
@@ -1254,7 +1286,13 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
 
 }  // namespace
 
+// A CREATE2 context walks salts, not keys: the key dispatches refuse it.
+static int refuse_create2(vgen_ctx *c, const char *what) {
+    return c->fail(VGEN_E_UNSUPPORTED, std::string(what) + ": an ethereum-create2 context tests salts, not keys - use vgen_dispatch_create2 (vgen_scan_create2)");
+}
+
 int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
+    if (c->format == VGF_ETHEREUM_CREATE2) return refuse_create2(c, "vgen_dispatch");
     if (frame >= c->frames || !start_key_be) return c->fail(VGEN_E_INVALID, "bad frame index / key");
     vgen_ctx::Frame &f = c->fr[frame];
     if (f.in_flight) return c->fail(VGEN_E_STATE, "frame already has a dispatch in flight");
@@ -1363,6 +1401,7 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
 }
 
 int rt_dispatch_keys(vgen_ctx *c, uint32_t frame, const uint8_t *keys_be, uint32_t n) {
+    if (c->format == VGF_ETHEREUM_CREATE2) return refuse_create2(c, "vgen_dispatch_keys");
     if (frame >= c->frames || !keys_be) return c->fail(VGEN_E_INVALID, "bad frame index / key buffer");
     if (n == 0 || n > c->batch) return c->fail(VGEN_E_INVALID, "vgen_dispatch_keys: n must be in [1, batch_size]");
     vgen_ctx::Frame &f = c->fr[frame];
@@ -1378,7 +1417,67 @@ int rt_dispatch_keys(vgen_ctx *c, uint32_t frame, const uint8_t *keys_be, uint32
 
 // Independent random keys (the reference CPU path's shape, src/scanner.rs:144-155) with no upload: lane i draws
 // key(seed, stream, first_index + i) from the counter-based stream of core/rnd.h on the device.
+static int create2_set(vgen_ctx *c, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]) {
+    for (auto &fr : c->fr)
+        if (fr.in_flight) return c->fail(VGEN_E_STATE, "vgen_set_create2 while a dispatch is in flight");
+    uint8_t salt[32] = {0};
+    memcpy(salt, salt_prefix, 24);   // counter 0: the kernel ORs the counter's bytes into words 11 - 13
+    create2_message(deployer, salt, init_code_hash, c->create2_m);
+    c->have_create2 = true;
+    return VGEN_OK;
+}
+
+// One kernel per dispatch (plus the list path's kernels behind it where the filter needs them), on the frame's own stream.
+static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter) {
+    if (frame >= c->frames) return c->fail(VGEN_E_INVALID, "bad frame index");
+    if (!c->have_create2) return c->fail(VGEN_E_STATE, "vgen_dispatch_create2 before vgen_set_create2");
+    if (first_counter > UINT64_MAX - (c->batch - 1)) return c->fail(VGEN_E_RANGE, "vgen_dispatch_create2: the counter range passes 2^64 - 1");
+    vgen_ctx::Frame &f = c->fr[frame];
+    if (f.in_flight) return c->fail(VGEN_E_STATE, "frame already has a dispatch in flight");
+    if (c->injected_fault()) return c->fail(VGEN_E_HIP, "injected device failure (vgen_debug_fail_after)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = ensure_frame(c, frame)) return rc;
+    memset(&f.start, 0, sizeof f.start);
+    Create2Args a;
+    memset(&a, 0, sizeof a);
+    memcpy(a.m, c->create2_m, sizeof a.m);
+    a.first = first_counter;
+    const bool dump = dump_mode(c);
+    const bool inl = inline_filter(c);
+    const bool listed = list_mode(c) || deferred_filter(c);
+    PtabArgs p;
+    memset(&p, 0, sizeof p);
+    if (dump) {
+        if (int rc = ensure_dump_frame(c, frame)) return rc;
+        a.payloads = f.d_dump;
+    } else {
+        if (!f.d_list) return c->fail(VGEN_E_STATE, "the context's filter has no list buffers");   // (made by vgen_set_filter)
+        a.payloads = f.d_list;
+        if (inl) {
+            a.hits = f.d_hits;
+            a.filter = c->d_filter;
+            p.payloads = f.d_list;
+            p.hits = f.d_hits;
+            p.mhdr = reinterpret_cast<DevMatchHeader *>(f.d_match);
+            p.mrec = reinterpret_cast<DevMatch *>(f.d_match + sizeof(DevMatchHeader));
+            p.stride = p.count = c->batch;
+            p.images = 1;
+            p.match_base = f.match_base;
+            p.match_cap = c->match_cap;
+        }
+    }
+    if (c->timing) {
+        HIP_TRY(c, hipEventRecord(f.ev_start, f.s));
+        HIP_TRY(c, hipEventRecord(f.ev_mid, f.s));
+    }
+    HIP_TRY(c, launch_create2(a, c->batch, inl ? &p : nullptr, f.s));
+    if (listed)
+        if (int rc = enqueue_ptab(c, f, c->batch, false)) return rc;
+    return finish_dispatch(c, f, dump, c->batch, false);
+}
+
 int rt_dispatch_random(vgen_ctx *c, uint32_t frame, const RndSeed &seed, uint32_t stream, uint64_t first_index) {
+    if (c->format == VGF_ETHEREUM_CREATE2) return refuse_create2(c, "vgen_dispatch_random");
     if (frame >= c->frames) return c->fail(VGEN_E_INVALID, "bad frame index");
     if (first_index > UINT64_MAX - (c->batch - 1)) return c->fail(VGEN_E_RANGE, "vgen_dispatch_random: index range wraps 2^64");
     vgen_ctx::Frame &f = c->fr[frame];

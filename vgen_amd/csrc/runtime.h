@@ -77,6 +77,13 @@ struct vgen_ctx {
     uint32_t *d_chk_lut = nullptr;       // Bech32 checksum tables of the current filter (when it tests the checksum)
     bool have_filter = false;            // false = dump mode
     vg::DevFilter h_filter{};
+    // VGF_ETHEREUM_CREATE2: the 22 message words of salt counter 0 (vgen_set_create2)
+    uint32_t create2_m[22] = {0};
+    bool have_create2 = false;
+    // ... and the device side of such a context, set by the runtime that created it (nullptr on every other context): cabi.cpp and
+    // scanner.cpp reach the CREATE2 job and dispatch through these, so the rt_* interface below stays what the stand-in implements
+    int (*create2_set)(vgen_ctx *, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]) = nullptr;
+    int (*create2_dispatch)(vgen_ctx *, uint32_t frame, uint64_t first_counter) = nullptr;
     // DEVF_LIST: the list's interval table on the device (bitmap | offsets | lo | hi), and the frames' device-only payload
     // buffers + hit masks (made by vgen_set_filter when a list is first set: never on the dispatch path)
     uint8_t *d_ptab = nullptr;
@@ -198,6 +205,16 @@ int rt_clock_probe_read(vgen_ctx *ctx, double *mhz);
 // `cap` (vgen_scan_config.table_bits_max; 0 = none) bounds it by additions per multiplication.  A wider table than the one in use is
 // built in the background while the dispatches go on (runtime.cpp) and taken into use when complete: nothing waits for it.
 void rt_prefer_table_bits(vgen_ctx *ctx, uint32_t bits, uint32_t cap = 0);
+// CREATE2 contexts (VGF_ETHEREUM_CREATE2), through vgen_ctx::create2_set / create2_dispatch: the job's message of counter 0
+// (core/hash.h create2_message) and a dispatch of the counters first_counter .. first_counter + batch - 1 on `frame`.
+inline int rt_set_create2(vgen_ctx *ctx, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]) {
+    if (!ctx->create2_set) return ctx->fail(VGEN_E_INVALID, "vgen_set_create2: the context was not created for the ethereum-create2 format (7)");
+    return ctx->create2_set(ctx, deployer, init_code_hash, salt_prefix);
+}
+inline int rt_dispatch_create2(vgen_ctx *ctx, uint32_t frame, uint64_t first_counter) {
+    if (!ctx->create2_dispatch) return ctx->fail(VGEN_E_INVALID, "vgen_dispatch_create2: the context was not created for the ethereum-create2 format (7)");
+    return ctx->create2_dispatch(ctx, frame, first_counter);
+}
 int rt_get_memory(const vgen_ctx *ctx, vgen_memory_info *out);
 int rt_get_resources(const vgen_ctx *ctx, uint32_t *dump_frames, uint32_t *table_bits, uint32_t *table_bits_wanted, std::string *note);
 

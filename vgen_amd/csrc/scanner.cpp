@@ -661,6 +661,16 @@ int finish_result(vgen_ctx *ctx, uint32_t format, const MatchList &matches, uint
 
 }  // namespace
 
+// The key-walking scans do not serve a CREATE2 context or configuration: its candidates are salts.
+static int refuse_create2(vgen_ctx *ctx, const char *what) {
+    return ctx->fail(VGEN_E_UNSUPPORTED, std::string(what) + ": the ethereum-create2 format is searched by salt - use vgen_scan_create2");
+}
+static bool any_create2(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_scan_config &cfg) {
+    bool any = cfg.format == VGF_ETHEREUM_CREATE2;
+    for (uint32_t i = 0; i < n_ctx; i++) any = any || ctxs[i]->format == VGF_ETHEREUM_CREATE2;
+    return any;
+}
+
 // ABI 4's vgen_scan_config, or ABI 3's 136 bytes (no table_bits_max: no cap): -> the full structure, fields beyond the caller's zero.
 static bool normalise_scan_config(const vgen_scan_config *in, vgen_scan_config &full) {
     constexpr uint32_t CONFIG_ABI3 = 136;
@@ -676,6 +686,7 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
     vgen_scan_config c;   // (a checkpoint may give it the file's base key)
     if (!ctx || !pattern || !out || !normalise_scan_config(cfg_in, c)) return VGEN_E_INVALID;
     memset(out, 0, sizeof *out);
+    if (ctx->format == VGF_ETHEREUM_CREATE2 || c.format == VGF_ETHEREUM_CREATE2) return refuse_create2(ctx, "vgen_scan");
     const auto t0 = std::chrono::steady_clock::now();
     vgen_filter flt;
     std::string err;
@@ -915,6 +926,7 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
                                vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out) {
     vgen_scan_config cfg_full;
     if (!pattern || !multi_args(ctxs, n_ctx, cfg_in, cfg_full, out)) return VGEN_E_INVALID;
+    if (any_create2(ctxs, n_ctx, cfg_full)) return refuse_create2(ctxs[0], "vgen_scan_multi");
     const vgen_scan_config *cfg = &cfg_full;
     vgen_filter flt;
     std::string err;
@@ -930,6 +942,7 @@ extern "C" int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter
                               vgen_scan_result *out) {
     vgen_scan_config cfg_full;
     if (!list || !multi_args(ctxs, n_ctx, cfg_in, cfg_full, out)) return VGEN_E_INVALID;
+    if (any_create2(ctxs, n_ctx, cfg_full)) return refuse_create2(ctxs[0], "vgen_scan_list");
     if (!list->list) return ctxs[0]->fail(VGEN_E_INVALID, "vgen_scan_list needs a pattern list (vgen_filter_compile_list)");
     if (cfg_full.format != list->format) return ctxs[0]->fail(VGEN_E_INVALID, "scan format differs from the pattern list's format");
     cfg_full.case_insensitive = list->case_insensitive ? 1 : 0;   // the list carries it
@@ -940,6 +953,171 @@ extern "C" int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter
     ListLedger ll;
     ll.init(list, per_pattern, cfg_full.count, own_bases ? 1 : n_ctx);
     return scan_multi_run(ctxs, n_ctx, *list, id.c_str(), &cfg_full, cb, user, stop, out, &ll);
+}
+
+// ---- CREATE2: a search over salts (VGEN_FMT_ETHEREUM_CREATE2) --------------------------------------------------------------
+// A loop of its own, on the calling thread: global batch b = counters first_counter + b * batch .. goes to context b mod n_ctx, every
+// context keeps its frames full in dispatch order, and the batches are waited for and confirmed in global order, so the results
+// come in ascending counter order by construction.  No key arithmetic, no checkpoint, no take-over of a failed context.
+namespace {
+
+struct Create2Lane {
+    vgen_ctx *ctx = nullptr;
+    uint32_t nframes = 0;                 // frames driven: all of them, or those dump mode serves
+    uint32_t next_frame = 0;
+    uint64_t next = 0;                    // next global batch this context dispatches
+    uint64_t issued = 0;                  // batches dispatched and not abandoned: what max_batches counts
+    std::vector<std::pair<uint32_t, uint64_t>> fl;   // (frame, global batch) in flight, oldest first
+};
+
+// waits for everything the lane has in flight and forgets it (the scan is over, or the lane starts again from a batch)
+void create2_drain(Create2Lane &l) {
+    for (auto &fb : l.fl) (void)rt_wait(l.ctx, fb.first, nullptr, 0, nullptr, nullptr);
+    l.fl.clear();
+}
+
+}  // namespace
+
+extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const uint8_t deployer[20], const uint8_t init_code_hash[32],
+                                 const uint8_t salt_prefix[24], uint64_t first_counter, const vgen_scan_config *cfg_in, vgen_progress_cb cb,
+                                 void *user, const volatile int32_t *stop, vgen_scan_result *out) {
+    vgen_scan_config c;
+    if (!pattern || !deployer || !init_code_hash || !salt_prefix || !multi_args(ctxs, n_ctx, cfg_in, c, out)) return VGEN_E_INVALID;
+    vgen_ctx *c0 = ctxs[0];
+    if (c.format != VGF_ETHEREUM_CREATE2) return c0->fail(VGEN_E_INVALID, "vgen_scan_create2: the scan format must be ethereum-create2 (7)");
+    for (uint32_t i = 0; i < n_ctx; i++) {
+        if (ctxs[i]->format != VGF_ETHEREUM_CREATE2) return c0->fail(VGEN_E_INVALID, "vgen_scan_create2: a context was not created for the ethereum-create2 format (7)");
+        for (auto &f : ctxs[i]->fr)
+            if (f.in_flight) return c0->fail(VGEN_E_STATE, "vgen_scan_create2 while a dispatch is in flight");
+    }
+    if (c.has_start || c.has_end || c.seed || c.shard || c.n_shards > 1 || c.checkpoint_path || c.flags)
+        return c0->fail(VGEN_E_UNSUPPORTED, "vgen_scan_create2 reads format, count, case_insensitive and max_batches: start / end, seed, shards, checkpoints and flags do not apply to a salt search");
+    const auto t0 = std::chrono::steady_clock::now();
+    vgen_filter flt;
+    std::string err;
+    if (!filter_compile(pattern, c.case_insensitive != 0, c.format, flt, err)) return c0->fail(VGEN_E_PATTERN, err);
+    const bool dump = flt.dev.kind == DEVF_HOST_ALL;   // no device filter: every payload comes back and the host filters
+    const uint32_t batch = c0->batch;
+    // whole batches the counter space holds from first_counter on (a tail shorter than a batch is not tested)
+    const uint64_t n_batches = first_counter > UINT64_MAX - (batch - 1) ? 0 : (UINT64_MAX - (batch - 1) - first_counter) / batch + 1;
+    std::vector<Create2Lane> lanes(n_ctx);
+    int rc = VGEN_OK;
+    for (uint32_t i = 0; i < n_ctx && rc == VGEN_OK; i++) {
+        Create2Lane &l = lanes[i];
+        l.ctx = ctxs[i];
+        l.next = i;
+        l.nframes = l.ctx->frames;
+        if ((rc = rt_set_create2(l.ctx, deployer, init_code_hash, salt_prefix)) != VGEN_OK) break;
+        if ((rc = rt_set_filter(l.ctx, &flt)) != VGEN_OK) break;
+        if (dump) {
+            uint32_t df = 0;
+            if ((rc = rt_get_resources(l.ctx, &df, nullptr, nullptr, nullptr)) != VGEN_OK) break;
+            l.nframes = std::max(1u, std::min(l.nframes, df));
+        }
+    }
+    if (rc != VGEN_OK) {
+        if (c0->err.empty()) c0->err = "vgen_scan_create2: a context refused the job or the filter (vgen_last_error of that context)";
+        return rc;
+    }
+    auto stopped = [&]() { return stop && __atomic_load_n(const_cast<const int32_t *>(stop), __ATOMIC_RELAXED) != 0; };
+    ResultSink sink(c.count);
+    std::vector<vgen_match> recs;
+    uint64_t ops = 0, g = 0;   // g: the next global batch to finish
+    bool complete = false;
+    vgen_ctx *failed = nullptr;
+    auto fill = [&](Create2Lane &l) -> int {
+        while (l.fl.size() < l.nframes && l.next < n_batches && (c.max_batches == 0 || l.issued < c.max_batches)) {
+            if (int r = rt_dispatch_create2(l.ctx, l.next_frame, first_counter + l.next * batch)) return r;
+            l.fl.emplace_back(l.next_frame, l.next);
+            l.next_frame = (l.next_frame + 1) % l.nframes;
+            l.next += n_ctx;
+            l.issued++;
+        }
+        return VGEN_OK;
+    };
+    while (rc == VGEN_OK && !sink.done() && !stopped()) {
+        for (auto &l : lanes)
+            if ((rc = fill(l)) != VGEN_OK) {
+                failed = l.ctx;
+                break;
+            }
+        if (rc != VGEN_OK) break;
+        Create2Lane &l = lanes[g % n_ctx];
+        if (l.fl.empty()) {   // this context has nothing left to do: the counter space or its max_batches ran out
+            complete = g >= n_batches;
+            break;
+        }
+        const uint32_t frame = l.fl.front().first;
+        const uint64_t base = first_counter + g * batch;
+        uint32_t found = 0;
+        uint64_t tested = 0;
+        recs.resize(dump ? 0 : l.ctx->match_cap);
+        if ((rc = rt_wait(l.ctx, frame, recs.data(), (uint32_t)recs.size(), &found, &tested)) != VGEN_OK) {
+            l.fl.erase(l.fl.begin());
+            failed = l.ctx;
+            break;
+        }
+        l.fl.erase(l.fl.begin());
+        if (!dump && found > l.ctx->match_cap) {
+            // more candidates than the ring holds: this context starts again from batch g with rings for a whole batch
+            l.issued -= l.fl.size() + 1;
+            create2_drain(l);
+            l.next = g;
+            l.next_frame = 0;
+            if ((rc = rt_set_match_cap(l.ctx, batch)) != VGEN_OK) failed = l.ctx;
+            continue;
+        }
+        const uint8_t *view = nullptr;
+        if (dump && (rc = rt_dump_view(l.ctx, frame, &view, nullptr)) != VGEN_OK) {
+            failed = l.ctx;
+            break;
+        }
+        const uint32_t n = dump ? batch : found;
+        for (uint32_t k = 0; k < n && sink.wants_more(); k++) {
+            const uint32_t index = dump ? k : recs[k].index;
+            const uint8_t *payload = dump ? view + (size_t)k * 20 : reinterpret_cast<const uint8_t *>(recs[k].payload);
+            const std::string addr = address_from_payload(c.format, payload);
+            LiteMatch m;
+            if (addr.empty() || addr.size() >= sizeof m.address || !filter_accepts(flt, addr, payload)) continue;
+            memcpy(m.key, salt_prefix, 24);   // the "key" of a CREATE2 result is the salt
+            const uint64_t counter = base + index;
+            for (int b = 0; b < 8; b++) m.key[24 + b] = (uint8_t)(counter >> (8 * (7 - b)));
+            memcpy(m.address, addr.c_str(), addr.size() + 1);
+            sink.add(m);
+        }
+        sink.commit(g, tested);
+        ops += tested;
+        g++;
+        if (cb) cb(ops, user);
+    }
+    for (auto &l : lanes) create2_drain(l);
+    const std::string why = failed ? failed->err : std::string();
+    out->n_matches = sink.matches.size();
+    out->operations = ops;
+    if (!sink.matches.empty()) {
+        out->matches = (vgen_generated *)malloc(sink.matches.size() * sizeof(vgen_generated));
+        if (!out->matches) return c0->fail(VGEN_E_NOMEM, "out of memory");
+        size_t i = 0;
+        for (auto &blk : sink.matches.blocks())
+            for (const LiteMatch &m : blk) {
+                vgen_generated &r = out->matches[i++];
+                memset(&r, 0, sizeof r);
+                const std::string hex = "0x" + hex_lower(m.key, 32);
+                strncpy(r.address, m.address, sizeof r.address - 1);
+                strncpy(r.wif, hex.c_str(), sizeof r.wif - 1);
+                strncpy(r.hex, hex.c_str(), sizeof r.hex - 1);
+                r.format = c.format;
+                memcpy(r.key, m.key, 32);
+            }
+    }
+    out->elapsed_secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != VGEN_OK) {
+        out->failed_shards = 1;
+        c0->err = why;
+        return rc;
+    }
+    out->complete = complete ? 1 : 0;
+    return VGEN_OK;
 }
 
 extern "C" void vgen_scan_result_free(vgen_scan_result *r) {
