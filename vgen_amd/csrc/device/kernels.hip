@@ -1843,10 +1843,10 @@ static hipError_t launch_bwd(const SeqArgs &a, hipStream_t stream) {
     if (a.xs && !a.endo && (FMT == VGF_P2PKH || FMT == VGF_P2SH_P2WPKH)) {
         // the split form: point arithmetic (x and the prefix byte parked per key), then one key per lane through the hashes
         constexpr int HF = FMT == VGF_P2SH_P2WPKH ? VGF_P2SH_P2WPKH : VGF_P2PKH;
+        if (a.hash_kpl == 0 || (2 * a.s) % a.hash_kpl != 0) return hipErrorInvalidValue;   // (before the first launch: a refused dispatch runs nothing)
         hipLaunchKernelGGL((seq_bwd_kernel<VGF_P2PKH, false, false, false, true>), dim3(a.groups), dim3(WG), 0, stream, a);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        if (a.hash_kpl == 0 || (2 * a.s) % a.hash_kpl != 0) return hipErrorInvalidValue;
         if (full) hipLaunchKernelGGL((seq_hash_kernel<HF, true>), dim3(a.groups, 2 * a.s / a.hash_kpl), dim3(WG), a.dfa_bytes, stream, a);
         else hipLaunchKernelGGL((seq_hash_kernel<HF, false>), dim3(a.groups, 2 * a.s / a.hash_kpl), dim3(WG), 0, stream, a);
         return hipGetLastError();
