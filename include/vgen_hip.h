@@ -215,13 +215,43 @@ int vgen_filter_matches(const vgen_filter *f, const char *address);
  * prefilter; reference-equivalent host filtering), 1 = hash160 range test (Base58 prefixes),
  * 2 = masked-bits test (Bech32 / hex prefixes and suffixes), 3 = match-all, 4 = the pattern's whole DFA runs on the
  * device over the encoded address (unanchored patterns, Base58 suffixes), 5 = pattern list: the payloads stay on the
- * device and are looked up in a table of intervals of their top 64 bits (vgen_filter_compile_list). */
+ * device and are looked up in a table of intervals of their top 64 bits (vgen_filter_compile_list), 6 = score specification
+ * (below): the payloads are scored on the device by kernels of their own. */
 int vgen_filter_device_kind(const vgen_filter *f);
 /* Size in bytes of the automaton a kind-4 filter stages into LDS (at most 48 KiB; 0 for the other kinds).  With the
  * product tree (and, on a VGEN_FLAG_ENDO context of the uncompressed / Ethereum formats, the parked y coordinate)
  * beside it a workgroup must stay within 64 KiB of LDS: an ENDO dispatch whose automaton does not leave room for the
  * parked coordinate tests the plain keys only (vgen_wait then reports keys_tested = batch_size for it). */
 int vgen_filter_dfa_bytes(const vgen_filter *f);
+
+/* ---- score specifications (create2crunch / profanity: rank hex addresses by zero bytes and by leading or counted digits) ----
+ *
+ * For the hex formats (5, 6, 7) vgen_filter_compile also takes the reserved prefix "score:" followed by 1 to 4 terms joined by '&',
+ * each `<metric>>=<n>`.  (':' is in no address alphabet: as a regular expression such a string could never match.)  The metrics are
+ * functions of the 20-byte payload, i.e. of the 40 hex digits of the address; EIP-55 casing plays no part and case_insensitive is
+ * ignored:
+ *     zero-bytes           bytes equal to 0x00                                   0 .. 20
+ *     leading-zero-bytes   length of the leading run of 0x00 bytes               0 .. 20
+ *     leading:<h>          length of the leading run of hex digit h (0-9a-fA-F)  0 .. 40
+ *     count:<h>            hex digits equal to h                                 0 .. 40
+ * An address is accepted when every term holds; its SCORE is the value of the first term's metric.  n beyond the metric's range, a
+ * fifth term, an unknown metric and an empty term are VGEN_E_PATTERN (vgen_last_error(NULL) says which); any other format is
+ * VGEN_E_UNSUPPORTED; vgen_filter_compile_list refuses such lines.  The filter has device kind 6, vgen_filter_dfa_bytes 0 and
+ * vgen_filter_pattern_count 1; vgen_filter_matches / vgen_filter_which decode the address and evaluate the terms (a string that is no
+ * address of the format matches nothing).  vgen_pattern_difficulty is exact for one term - the reciprocal, rounded down, of a binomial
+ * tail with (20, 1/256) or (40, 1/16), or 256^n / 16^n for the leading runs - and for several terms the largest single-term value: a
+ * LOWER bound on the difficulty of the conjunction.  vgen_pattern_invalid_chars reports none.
+ * A context with such a filter dumps the payloads into the frames' device-only buffers (as for a pattern list: every frame can be
+ * used, vgen_memory_info.mode_bytes counts them) and scores them there; a format-7 context hashes and scores in one kernel.  Records
+ * are exact (every term holds), in index order.  An all-zero payload - the dump's mark for "no key" - is never reported.
+ *
+ * The score of `address` under a score filter.  VGEN_E_INVALID for another kind of filter and for a string that is not an address of
+ * the filter's format. */
+int vgen_score(const vgen_filter *f, const char *address, uint32_t *score);
+/* Replaces the first term's threshold for the dispatches enqueued after the call (the value is copied into each dispatch's kernel
+ * arguments when it is enqueued, so the call is allowed while dispatches are in flight).  VGEN_E_STATE when the installed filter is
+ * not a score filter, VGEN_E_PATTERN when min is beyond the metric's range.  vgen_set_filter resets it to the filter's own value. */
+int vgen_set_score_min(vgen_ctx *ctx, uint32_t min);
 
 /* ---- pattern lists (VanitySearch -i / vanitygen -f: many patterns, one scan) ----------------------------------------
  *
@@ -445,6 +475,15 @@ typedef struct vgen_scan_config {
                                       one multiplication for the six: 5.5 instead of 1.35 Gkeys/s); seeds and shards keep their
                                       meaning there (they name streams of candidates, not ranges). */
 
+#define VGEN_SCAN_BEST 2u          /* score specifications only (any other pattern: VGEN_E_INVALID): a candidate is a result only if its
+                                      score is strictly higher than the score of every result before it in the scan's result order -
+                                      batches in order, keys (counters) ascending within a batch.  Results have strictly rising scores
+                                      and a seeded or range scan is reproducible.  After every improvement the scan raises the
+                                      contexts' threshold (vgen_set_score_min(best + 1)); what dispatches already in flight still
+                                      deliver under the older threshold is discarded.  count, the stop flag, max_batches and the
+                                      end of the range end the scan as usual; so does a score that cannot be improved on.
+                                      With checkpoint_path: VGEN_E_UNSUPPORTED.  vgen_scan_create2 accepts this one flag. */
+
 /* GeneratedAddress (src/address.rs:63-72). */
 typedef struct vgen_generated {
     char address[96];
@@ -506,7 +545,8 @@ int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter *list, uin
  * first_counter + b * batch_size .. and goes to context b mod n_ctx; device candidates are confirmed on the host with the exact
  * automaton (a pattern without a device filter is filtered on the host from dumps); results come in ascending counter order,
  * truncated to cfg->count; operations count batch_size per finished batch.  From cfg: format (must be 7), count, case_insensitive,
- * max_batches (per context); a set has_start, has_end, seed, shard, n_shards > 1, checkpoint_path or flags is VGEN_E_UNSUPPORTED.
+ * max_batches (per context), flags (VGEN_SCAN_BEST only); a set has_start, has_end, seed, shard, n_shards > 1, checkpoint_path or any
+ * other flag is VGEN_E_UNSUPPORTED.
  * complete = 1 when the 64-bit counter space ran out.  The job is installed on every context (vgen_set_create2).
  * In a result: address = the EIP-55 address, key = the 32-byte SALT, hex = wif = "0x" + the salt in lowercase hex, format = 7.
  * Not provided for this format: checkpoints / resuming, pattern-list scans, take-over of a failed context's stripe. */

@@ -82,6 +82,7 @@ class _ScanConfig(ctypes.Structure):
 
 
 SCAN_RANDOM_KEYS = 1   # VGEN_SCAN_RANDOM_KEYS
+SCAN_BEST = 2          # VGEN_SCAN_BEST
 
 
 class _Generated(ctypes.Structure):
@@ -151,6 +152,8 @@ _L.vgen_create2_address.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_c
 _L.vgen_create2_salt.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
 _L.vgen_set_create2.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
 _L.vgen_dispatch_create2.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]
+_L.vgen_score.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32)]
+_L.vgen_set_score_min.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
 _L.vgen_scan_create2.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                  ctypes.c_uint64, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                  ctypes.POINTER(_ScanResult)]
@@ -360,10 +363,26 @@ class Pattern:
     def is_case_insensitive(self) -> bool:
         return self.case_insensitive
 
+    def score(self, address: str) -> int:
+        """vgen_score: the score of `address` under a score specification ("score:zero-bytes>=2&leading:0>=4": the value of the
+        first term's metric).  VgenError for any other pattern and for a string that is no address of the format."""
+        v = ctypes.c_uint32()
+        rc = _L.vgen_score(self._h, address.encode(), ctypes.byref(v))
+        if rc < 0:
+            raise VgenError(rc, "vgen_score: not a score specification, or not an address of its format")
+        return v.value
+
     def __del__(self):
         if getattr(self, "_h", None):
             _L.vgen_filter_free(self._h)
             self._h = None
+
+
+def score(filter_or_spec, address: str, fmt: AddressFormat = AddressFormat.Ethereum) -> int:
+    """The score of `address` under a score specification: a Pattern compiled from one, or the specification's text (compiled for
+    `fmt`, one of the three hex formats)."""
+    p = filter_or_spec if isinstance(filter_or_spec, Pattern) else Pattern(filter_or_spec, fmt=fmt)
+    return p.score(address)
 
 
 class PatternList:
@@ -473,6 +492,7 @@ class ScanConfig:
     checkpoint_interval_ms: int = 0
     random_keys: bool = False       # VGEN_SCAN_RANDOM_KEYS: an independent random key per candidate (scanner.rs:118-169's shape)
     table_bits_max: int = 0         # widest generator table the scan may move the context to (0 = the context's memory policy decides)
+    best: bool = False              # VGEN_SCAN_BEST (score specifications): report only results that beat every score reported before
 
 
 @dataclass
@@ -548,6 +568,10 @@ class GpuRunner:
     def set_create2(self, job: "Create2Job"):
         """vgen_set_create2: the job of an EthereumCreate2 runner."""
         _check(_L.vgen_set_create2(self._h, job.deployer, job.init_code_hash, job.salt_prefix), self._h)
+
+    def set_score_min(self, minimum: int):
+        """vgen_set_score_min: the first term's threshold of the installed score filter, for dispatches enqueued from now on."""
+        _check(_L.vgen_set_score_min(self._h, minimum), self._h)
 
     def dispatch_create2(self, first_counter: int, frame: int):
         """vgen_dispatch_create2: salts first_counter .. first_counter + batch_size - 1 of the job; results as for dispatch()."""
@@ -644,7 +668,7 @@ def _scan_config(config: ScanConfig) -> _ScanConfig:
     if config.checkpoint_path:
         c.checkpoint_path = os.fsencode(config.checkpoint_path)
         c.checkpoint_interval_ms = config.checkpoint_interval_ms
-    c.flags = SCAN_RANDOM_KEYS if config.random_keys else 0
+    c.flags = (SCAN_RANDOM_KEYS if config.random_keys else 0) | (SCAN_BEST if config.best else 0)
     c.table_bits_max = config.table_bits_max
     return c
 

@@ -83,6 +83,10 @@ int vgen_get_memory(const vgen_ctx *ctx, vgen_memory_info *out) {
 
 int vgen_filter_compile(const char *pattern, int case_insensitive, uint32_t format, vgen_filter **out) {
     if (!pattern || !out) return VGEN_E_INVALID;
+    if (vg::score_spec_unsupported(pattern, format)) {
+        g_last_error = vg::SCORE_FORMATS_MESSAGE;
+        return VGEN_E_UNSUPPORTED;
+    }
     vgen_filter *f = new vgen_filter();
     std::string err;
     if (!vg::filter_compile(pattern, case_insensitive != 0, format, *f, err)) {
@@ -98,7 +102,7 @@ void vgen_filter_free(vgen_filter *f) { delete f; }
 
 int vgen_filter_matches(const vgen_filter *f, const char *address) {
     if (!f || !address) return VGEN_E_INVALID;
-    if (f->list) return vg::filter_accepts(*f, address, nullptr) ? 1 : 0;
+    if (f->list || f->score.n) return vg::filter_accepts(*f, address, nullptr) ? 1 : 0;
     return f->dfa.is_match(address) ? 1 : 0;
 }
 
@@ -206,7 +210,28 @@ int vgen_set_match_cap(vgen_ctx *ctx, uint32_t match_cap) {
 
 int vgen_set_filter(vgen_ctx *ctx, const vgen_filter *f) {
     if (!ctx) return VGEN_E_INVALID;
-    return vg::rt_set_filter(ctx, f);
+    const int rc = vg::rt_set_filter(ctx, f);
+    if (rc != VGEN_OK) return rc;
+    // a score filter's terms (n = 0 for every other filter): the runtime installs them itself; repeated here so that a stand-in of the
+    // runtime that knows nothing of score filters (tests/native) leaves the context in the same state
+    if (f) ctx->score = f->score;
+    else memset(&ctx->score, 0, sizeof ctx->score);
+    return VGEN_OK;
+}
+
+int vgen_set_score_min(vgen_ctx *ctx, uint32_t min) {
+    if (!ctx) return VGEN_E_INVALID;
+    if (!ctx->have_filter || ctx->score.n == 0)   // (the terms are installed by vgen_set_filter, for a score filter only)
+        return ctx->fail(VGEN_E_STATE, "vgen_set_score_min: the installed filter is not a score filter");
+    if (min > vg::score_metric_max(ctx->score.t[0].metric))
+        return ctx->fail(VGEN_E_PATTERN, "vgen_set_score_min: the first term's metric is at most " + std::to_string(vg::score_metric_max(ctx->score.t[0].metric)));
+    ctx->score.t[0].min = min;
+    return VGEN_OK;
+}
+
+int vgen_score(const vgen_filter *f, const char *address, uint32_t *score) {
+    if (!f || !address || !score || f->score.n == 0) return VGEN_E_INVALID;
+    return vg::score_of(*f, address, nullptr, score, nullptr) ? VGEN_OK : VGEN_E_INVALID;
 }
 
 int vgen_dispatch(vgen_ctx *ctx, uint32_t frame, const uint8_t start_key_be[32]) {

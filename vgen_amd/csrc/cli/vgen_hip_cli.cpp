@@ -40,6 +40,7 @@ struct Opts {
     uint64_t per_pattern = 1;                 // --per-pattern (0 = unbounded)
     bool no_endo = false;
     bool random_keys = false;
+    bool best = false;                        // --best (score specifications): VGEN_SCAN_BEST
     uint32_t batch = 1u << 20, frames = 12;   // twelve frames own twelve hardware queues (runtime.cpp)
     uint32_t table_bits_max = 0;              // vgen_scan_config.table_bits_max (0 = the context's memory policy decides)
     uint64_t mem_budget = 0;                  // vgen_params.device_mem_budget_bytes (0 = automatic)
@@ -215,6 +216,10 @@ void usage() {
             "                    [--salt-prefix 0xHEX] [--salt-start N] [-c COUNT] [-i] [--devices ..] [-o ..]   (CREATE2, EIP-1014: searches the\n"
             "                    SALT salt_prefix (up to 24 bytes, zero padded) || 8-byte counter from N on; the printed key is the salt, and the\n"
             "                    address exists only when exactly this deployer runs CREATE2 with exactly this init code)\n"
+            "  vgen-hip generate -f ethereum|ethereum-contract|ethereum-create2 -p 'score:TERM[&TERM..]' [--best] ...   (rank hex addresses: up to\n"
+            "                    four terms METRIC>=N with the metrics zero-bytes, leading-zero-bytes, leading:H and count:H (H a hex digit);\n"
+            "                    results carry a score, the value of the first term's metric.  --best reports only results that beat every\n"
+            "                    score before them, -c then bounds the number of improvements.  range and estimate take such a pattern too)\n"
             "  vgen-hip generate --patterns-file FILE [--per-pattern N] ...   (instead of -p: one start-anchored prefix per line,\n"
             "                    one scan; N results per pattern (default 1, 0 = unbounded), -c caps the total (default: none);\n"
             "                    each result's pattern field is the lowest-index line it satisfies.  range takes it too)\n"
@@ -306,6 +311,7 @@ Opts parse(int argc, char **argv) {
         else if (a == "--no-gpu") o.no_gpu = true;
         else if (a == "--no-endo") o.no_endo = true;
         else if (a == "--random-keys") o.random_keys = true;
+        else if (a == "--best") o.best = true;
         else if (a == "--no-tui" || a == "--tui") {}                                   // no TUI in this build
         else if (a == "-l" || a == "--prefix-length") o.prefix_length = strtol(val().c_str(), nullptr, 10);
         else if (a == "--provider-table") o.provider_table = val();
@@ -623,6 +629,16 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         if (has_range) die("--random-keys draws an independent key per candidate: no range");
         cfg.flags |= VGEN_SCAN_RANDOM_KEYS;
     }
+    // -p 'score:...': results carry their score; --best reports every new best score as it turns up (-c bounds the number of
+    // improvements; without -c the search runs to the end of its range, a score that cannot be beaten, or Ctrl-C)
+    vgen_filter *score_flt = nullptr;
+    if (!list && pattern.compare(0, 6, "score:") == 0 && vgen_filter_compile(pattern.c_str(), 0, (uint32_t)fmt, &score_flt) != VGEN_OK) die(vgen_last_error(nullptr));
+    if (o.best) {
+        if (!score_flt) die("the argument '--best' needs a score specification as the pattern (-p 'score:zero-bytes>=1')");
+        if (!o.checkpoint.empty()) die("the argument '--best' cannot be used with '--checkpoint'");
+        cfg.flags |= VGEN_SCAN_BEST;
+        if (!o.count_given) cfg.count = UINT64_MAX;
+    }
 
     std::vector<vgen_generated> all;
     uint64_t total_ops = 0;
@@ -665,7 +681,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
     const double rate = total_secs > 0 ? (double)total_ops / total_secs : 0.0;
     const std::string fmt_name = format_display(fmt);
     if (o.output == "csv" && !all.empty())
-        fprintf(w, "address,wif,private_key_hex,format,pattern,operations,elapsed_secs,rate\n");
+        fprintf(w, "address,wif,private_key_hex,format,pattern,operations,elapsed_secs,rate%s\n", score_flt ? ",score" : "");
     for (size_t idx = 0; idx < all.size(); idx++) {
         const vgen_generated &g = all[idx];
         const std::string pattern = list ? list_pattern_of(list, g.address) : pattern_arg;
@@ -679,6 +695,8 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             snprintf(deployer, sizeof deployer, "%s", hex0x(job.deployer, 20).c_str());
             c2_hash = hex0x(job.init_code_hash, 32);
         }
+        uint32_t score = 0;   // (score searches only: every other output stays byte for byte what it was)
+        if (score_flt && vgen_score(score_flt, g.address, &score) != VGEN_OK) die("a result of a score search has no score");
         if (o.output == "text") {
             fprintf(w, "=== Match %zu of %zu ===\n", idx + 1, all.size());
             if (create2) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSalt    : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex);
@@ -686,6 +704,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
                          fmt_name.c_str(), g.address, g.wif, g.hex);
             if (create2) fprintf(w, "Deployer: %s  (the factory that must run CREATE2 with the salt above)\nInitHash: %s\n", deployer, c2_hash.c_str());
             else if (deployer[0]) fprintf(w, "Deployer: %s  (the account of this key; its first transaction must create the contract)\n", deployer);
+            if (score_flt) fprintf(w, "Score   : %u\n", score);
             if (!o.quiet) {
                 fprintf(w, "Ops     : %s (%.0f/sec)\n", with_commas(total_ops).c_str(), rate);
                 fprintf(w, "Time    : %s\n", format_duration(total_secs).c_str());
@@ -697,6 +716,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             fprintf(w, "{%s\"address\":%s%s,", nl, sp, json_str(g.address).c_str());
             if (deployer[0]) fprintf(w, "%s\"deployer\":%s%s,", nl, sp, json_str(deployer).c_str());
             if (create2) fprintf(w, "%s\"init_code_hash\":%s%s,", nl, sp, json_str(c2_hash).c_str());
+            if (score_flt) fprintf(w, "%s\"score\":%s%u,", nl, sp, score);
             fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
                        "\"operations\":%s%llu,%s\"elapsed_secs\":%s%s,%s\"rate\":%s%s%s}\n",
                     nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str(), nl,
@@ -704,15 +724,18 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
                     (unsigned long long)total_ops, nl, sp, json_f64(total_secs).c_str(), nl, sp, json_f64(rate).c_str(),
                     pretty ? "\n" : "");
         } else if (o.output == "csv") {
-            fprintf(w, "%s,%s,%s,%s,%s,%llu,%s,%s\n", csv_escape(g.address).c_str(), csv_escape(g.wif).c_str(),
+            fprintf(w, "%s,%s,%s,%s,%s,%llu,%s,%s", csv_escape(g.address).c_str(), csv_escape(g.wif).c_str(),
                     csv_escape(g.hex).c_str(), csv_escape(fmt_name).c_str(), csv_escape(pattern).c_str(),
                     (unsigned long long)total_ops, json_f64(total_secs).c_str(), json_f64(rate).c_str());
+            if (score_flt) fprintf(w, ",%u", score);
+            fprintf(w, "\n");
         } else if (o.output == "minimal") {
             fprintf(w, "%s\n", g.wif);
         } else {
             die("invalid value '" + o.output + "' for '--output'");
         }
     }
+    vgen_filter_free(score_flt);
     if (w != stdout) {
         fclose(w);
         if (!all.empty() && !o.quiet) fprintf(stderr, "Wrote %zu result(s) to %s\n", all.size(), o.file.c_str());

@@ -33,8 +33,10 @@ enum : uint32_t {
     DEVF_MASKED = 2,     // any t:  (H & mask_t) == value_t     (Bech32 / hex prefixes & suffixes)
     DEVF_ALL = 3,        // pattern accepts every address
     DEVF_DFA = 4,        // full match on the device: encode the address, walk the DFA (core/dfa_eval.h)
-    DEVF_LIST = 5        // pattern list: the payloads are dumped on the device and looked up in a table of intervals
+    DEVF_LIST = 5,       // pattern list: the payloads are dumped on the device and looked up in a table of intervals
                          // (core/ptab_eval.h, DevPtab); not evaluated through DevFilter
+    DEVF_SCORE = 6       // score specification (hex formats): the payloads are scored by kernels of their own (core/score_eval.h,
+                         // ScoreTerms by value in the kernel arguments); the rest of DevFilter is unused
 };
 
 constexpr uint32_t DEVF_MAX_TESTS = 64;
@@ -209,6 +211,44 @@ struct KeysArgs {
     uint32_t *xyz;             // scratch: Jacobian results, limb-major [27][groups * KEYS_WG] (X, Y, Z limbs; the taproot stage: X, validity word, Z)
     uint32_t *tree;            // scratch: product-tree nodes [groups][9][KEYS_WG]
     uint32_t *root;            // scratch: tree roots / their inverses [9][groups]
+};
+
+// ---- score searches (DEVF_SCORE; appended: no structure above changes) ----------------------------------------------------------
+// A score specification: 1 - 4 terms `metric >= min`, all of which must hold; the SCORE of a payload is the value of the first
+// term's metric (core/score_eval.h).  Plain data: a host-side field of vgen_filter / vgen_ctx, by value in the kernel arguments.
+enum : uint32_t {
+    SCORE_ZERO_BYTES = 0,          // bytes equal to 0x00                      0 .. 20
+    SCORE_LEADING_ZERO_BYTES = 1,  // length of the leading run of 0x00 bytes   0 .. 20
+    SCORE_LEADING_DIGIT = 2,       // length of the leading run of hex digit d  0 .. 40
+    SCORE_COUNT_DIGIT = 3          // hex digits equal to d                     0 .. 40
+};
+constexpr uint32_t SCORE_MAX_TERMS = 4;
+constexpr uint32_t score_metric_max(uint32_t metric) { return metric <= SCORE_LEADING_ZERO_BYTES ? 20u : 40u; }
+
+struct ScoreTerms {
+    uint32_t n;
+    struct {
+        uint32_t metric, digit, min;
+    } t[SCORE_MAX_TERMS];
+};
+
+// Arguments of payload_score_kernel: the geometry of payload_filter_kernel (images x stride slots, the first `count` of every image
+// written).  One ballot per wave goes into `hits`; ptab_compact_kernel, with PtabArgs over the same two buffers, follows.
+struct ScoreArgs {
+    ScoreTerms terms;
+    const uint32_t *payloads;    // slot s at payloads + 5 s
+    unsigned long long *hits;    // one bit per slot
+    uint32_t stride, count, images;
+};
+
+// Arguments of create2_score_kernel: the message and first counter of Create2Args (lane i tests counter first + i and owns slot i),
+// the terms, the hit mask and where the hit lanes' payloads go; the compaction follows here too.
+struct Create2ScoreArgs {
+    ScoreTerms terms;
+    uint32_t m[22];
+    unsigned long long first;
+    uint32_t *out;               // payloads of hit lanes only, slot i at out + 5 i
+    unsigned long long *hits;    // one bit per slot (batch / 64 words)
 };
 
 }  // namespace vg

@@ -2086,3 +2086,88 @@ hipError_t launch_create2(const Create2Args &a, uint32_t batch, const PtabArgs *
 }
 
 }  // namespace vg
+
+// ---- score searches (DEVF_SCORE) ---------------------------------------------------------------------------------------------
+// A score specification ("score:zero-bytes>=2&leading:0>=4") is evaluated by kernels of their own, not through filter_eval_n, which
+// every matching kernel above carries: the terms travel by value in the kernel arguments (scalar loads from the kernarg segment) and
+// the five payload words are scored in registers (core/score_eval.h).  Both kernels hand a hit mask to ptab_compact_kernel, like the
+// list lookup: one plain 64-bit store per wave, no atomics, no LDS.
+#include "../core/score_eval.h"
+
+namespace vg {
+
+// Formats 5 and 6: the per-key kernels dumped the payloads into the frame's device-only buffer (as for a pattern list); one thread
+// per slot scores it.  An all-zero payload is the dump's "no key" mark (it would score 20 zero bytes) and a slot at or beyond
+// `count` holds whatever an earlier dispatch left: neither is ever a candidate.
+__global__ void __launch_bounds__(256) payload_score_kernel(const ScoreArgs a) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    const size_t slot = (size_t)blockIdx.y * a.stride + i;
+    bool hit = false;
+    if (i < a.count) {
+        const u32 *p = a.payloads + slot * 5;
+        u32 pl[5];
+#pragma unroll
+        for (int k = 0; k < 5; k++) pl[k] = p[k];
+        hit = (pl[0] | pl[1] | pl[2] | pl[3] | pl[4]) != 0u && score_eval(a.terms, pl, nullptr);
+    }
+    const unsigned long long m = __ballot(hit);
+    if ((threadIdx.x & 63u) == 0) a.hits[slot >> 6] = m;
+}
+
+// Format 7, fused: create2_kernel<false> with the score in place of the prefilter (its few lines are repeated here so that
+// create2_kernel's two symbols stay what they are).
+__global__ void __launch_bounds__(256) create2_score_kernel(const Create2ScoreArgs a) {
+#if VG_BASE_PRIO && VG_KECCAK_BLOCK
+    __builtin_amdgcn_s_setprio(VG_BASE_PRIO);   // (the level the hash block returns to)
+#endif
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    u32 m[22];
+#pragma unroll
+    for (int k = 0; k < 22; k++) m[k] = a.m[k];
+    create2_place_counter(m, a.first + i);
+    u32 pl[5];
+#if VG_KECCAK_BLOCK
+    keccak_create2_block(m, pl);
+#else
+    keccak256_create2_addr(m, pl);
+#endif
+    const bool hit = score_eval(a.terms, pl, nullptr);
+    const unsigned long long mask = __ballot(hit);
+    if ((threadIdx.x & 63u) == 0) a.hits[i >> 6] = mask;
+    if (hit) {
+        u32 *o = a.out + (size_t)i * 5;
+#pragma unroll
+        for (int k = 0; k < 5; k++) o[k] = pl[k];
+    }
+}
+
+static bool score_terms_ok(const ScoreTerms &t) {
+    if (t.n == 0 || t.n > SCORE_MAX_TERMS) return false;
+    for (uint32_t k = 0; k < t.n; k++)
+        if (t.t[k].metric > SCORE_COUNT_DIGIT || t.t[k].digit > 15 || t.t[k].min > score_metric_max(t.t[k].metric)) return false;
+    return true;
+}
+
+hipError_t launch_payload_score(const ScoreArgs &a, const PtabArgs &compact, hipStream_t stream) {
+    if (a.stride == 0 || a.stride % 256 != 0 || a.count > a.stride || a.images == 0 || !a.payloads || !a.hits || !score_terms_ok(a.terms)) return hipErrorInvalidValue;
+    if (compact.payloads != a.payloads || compact.hits != a.hits || compact.stride != a.stride || compact.images != a.images || !compact.mhdr || !compact.mrec)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(payload_score_kernel, dim3(a.stride / 256, a.images), dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ptab_compact_kernel<5>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, compact);
+    return hipGetLastError();
+}
+
+hipError_t launch_create2_score(const Create2ScoreArgs &a, uint32_t batch, const PtabArgs &compact, hipStream_t stream) {
+    if (batch == 0 || batch % 256 != 0 || !a.out || !a.hits || !score_terms_ok(a.terms)) return hipErrorInvalidValue;
+    if (compact.payloads != a.out || compact.hits != a.hits || compact.stride != batch || compact.images != 1 || !compact.mhdr || !compact.mrec)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(create2_score_kernel, dim3(batch / 256), dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ptab_compact_kernel<5>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, compact);
+    return hipGetLastError();
+}
+
+}  // namespace vg

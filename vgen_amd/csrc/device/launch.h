@@ -53,4 +53,10 @@ hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream)
 // with launch_ptab (pattern list, on-device automaton).  Otherwise the kernel evaluates a.filter itself, writes a.hits and the
 // payloads of hit lanes, and the list path's compaction (*compact: the same payloads and hit mask, the frame's ring) makes the records.
 hipError_t launch_create2(const Create2Args &a, uint32_t batch, const PtabArgs *compact, hipStream_t stream);
+// A score dispatch (DEVF_SCORE, core/score_eval.h).  Formats 5 and 6: payload_score_kernel over the payloads the per-key kernels dumped
+// (a.payloads, a.stride / a.count / a.images as for launch_ptab), then the list path's compaction.  Format 7: create2_score_kernel over
+// `batch` (a multiple of 256) counters from a.first on, which writes the hit lanes' payloads to a.out, then the compaction.  `compact` must
+// name the same payload buffer, hit mask and geometry; a refused call launches nothing.
+hipError_t launch_payload_score(const ScoreArgs &a, const PtabArgs &compact, hipStream_t stream);
+hipError_t launch_create2_score(const Create2ScoreArgs &a, uint32_t batch, const PtabArgs &compact, hipStream_t stream);
 }  // namespace vg

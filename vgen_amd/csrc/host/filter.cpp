@@ -4,6 +4,7 @@
 #include "../core/dfa_eval.h"
 #include "../core/filter_eval.h"
 #include "../core/ptab_eval.h"
+#include "../core/score_eval.h"
 #include "encode.h"
 
 #include <string.h>
@@ -494,12 +495,153 @@ bool build_dfa_blob(const Dfa &d, const char *head, const char *alphabet, std::v
 
 }  // namespace
 
+// ---- score specifications -----------------------------------------------------------------------------------------
+
+bool is_score_spec(const std::string &pattern) { return pattern.compare(0, 6, "score:") == 0; }
+
+bool score_parse(const std::string &spec, ScoreTerms &out, std::string &err) {
+    memset(&out, 0, sizeof out);
+    if (!is_score_spec(spec)) {
+        err = "a score specification starts with 'score:'";
+        return false;
+    }
+    size_t pos = 6;
+    for (;;) {
+        size_t e = spec.find('&', pos);
+        if (e == std::string::npos) e = spec.size();
+        const std::string term = spec.substr(pos, e - pos);
+        const std::string at = "score term " + std::to_string(out.n + 1) + ": ";
+        if (term.empty()) {
+            err = at + "empty (terms are '<metric>>=<n>' joined by '&')";
+            return false;
+        }
+        if (out.n == SCORE_MAX_TERMS) {
+            err = "a score specification has at most " + std::to_string(SCORE_MAX_TERMS) + " terms";
+            return false;
+        }
+        const size_t ge = term.find(">=");
+        if (ge == std::string::npos || ge == 0) {
+            err = at + "'" + term + "' is not '<metric>>=<n>'";
+            return false;
+        }
+        const std::string metric = term.substr(0, ge), num = term.substr(ge + 2);
+        auto &t = out.t[out.n];
+        auto hex_digit = [](char c) -> int {
+            const char *q = c ? strchr(HEXL, (char)tolower((unsigned char)c)) : nullptr;
+            return q ? (int)(q - HEXL) : -1;
+        };
+        if (metric == "zero-bytes") {
+            t.metric = SCORE_ZERO_BYTES;
+        } else if (metric == "leading-zero-bytes") {
+            t.metric = SCORE_LEADING_ZERO_BYTES;
+        } else if ((metric.compare(0, 8, "leading:") == 0 && metric.size() == 9 && hex_digit(metric[8]) >= 0) ||
+                   (metric.compare(0, 6, "count:") == 0 && metric.size() == 7 && hex_digit(metric[6]) >= 0)) {
+            t.metric = metric[0] == 'l' ? SCORE_LEADING_DIGIT : SCORE_COUNT_DIGIT;
+            t.digit = (uint32_t)hex_digit(metric.back());
+        } else {
+            err = at + "unknown metric '" + metric + "' (zero-bytes, leading-zero-bytes, leading:<hex digit>, count:<hex digit>)";
+            return false;
+        }
+        if (num.empty() || num.size() > 3 || num.find_first_not_of("0123456789") != std::string::npos) {
+            err = at + "'" + num + "' is not a number";
+            return false;
+        }
+        t.min = (uint32_t)atoi(num.c_str());
+        if (t.min > score_metric_max(t.metric)) {
+            err = at + "'" + metric + "' is at most " + std::to_string(score_metric_max(t.metric));
+            return false;
+        }
+        out.n++;
+        if (e == spec.size()) break;
+        pos = e + 1;
+    }
+    return true;
+}
+
+namespace {
+
+U256 div_small(const U256 &a, uint32_t d) {   // exact or rounded down
+    U256 r;
+    unsigned __int128 rem = 0;
+    for (int i = 3; i >= 0; i--) {
+        const unsigned __int128 cur = (rem << 64) | a.w[i];
+        r.w[i] = (uint64_t)(cur / d);
+        rem = cur % d;
+    }
+    return r;
+}
+
+// payloads (of 2^160) on which one term holds
+U256 score_term_payloads(uint32_t metric, uint32_t min) {
+    const bool bytes = metric == SCORE_ZERO_BYTES || metric == SCORE_LEADING_ZERO_BYTES;
+    const uint32_t N = bytes ? 20 : 40, other = bytes ? 255 : 15, bits = bytes ? 8 : 4;
+    if (metric == SCORE_LEADING_ZERO_BYTES || metric == SCORE_LEADING_DIGIT) return U256::pow2(160 - bits * min);
+    // sum over k = min .. N of C(N, k) * other^(N - k):  term_N = 1, term_(k-1) = term_k * other * k / (N - k + 1)
+    U256 term = U256::from_u64(1), sum;
+    for (uint32_t k = N;; k--) {
+        if (k >= min) sum = add(sum, term);
+        if (k == 0 || k <= min) break;
+        term = div_small(mul_small(term, other * k), N - k + 1);
+    }
+    return sum;
+}
+
+}  // namespace
+
+void score_odds(const ScoreTerms &s, double *selectivity, uint64_t *difficulty) {
+    U256 t = U256::pow2(160);
+    for (uint32_t k = 0; k < s.n && k < SCORE_MAX_TERMS; k++) t = umin(t, score_term_payloads(s.t[k].metric, s.t[k].min));
+    if (selectivity) *selectivity = to_double(t) / 1461501637330902918203684832716283019655932542976.0;   // 2^160
+    if (!difficulty) return;
+    // floor(2^160 / t) by long division, saturating
+    unsigned __int128 q = 0;
+    U256 r;
+    for (int bit = 160; bit >= 0; bit--) {
+        r = add(r, r);
+        if (bit == 160) r.w[0] |= 1;
+        q <<= 1;
+        if (cmp(r, t) >= 0) {
+            r = sub(r, t);
+            q |= 1;
+        }
+        if (q >> 64) break;
+    }
+    *difficulty = (q >> 64) ? UINT64_MAX : (uint64_t)q;
+}
+
+bool score_of(const vgen_filter &f, const std::string &address, const uint8_t *payload, uint32_t *score, bool *accepted) {
+    if (f.score.n == 0) return false;
+    uint8_t buf[32];
+    if (!payload) {
+        if (!payload_from_address(f.format, address, buf)) return false;
+        payload = buf;
+    }
+    u32 w[5];
+    memcpy(w, payload, 20);
+    u32 sc = 0;
+    const bool ok = score_eval(f.score, w, &sc);
+    if (score) *score = sc;
+    if (accepted) *accepted = ok;
+    return true;
+}
+
 bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t format, vgen_filter &out,
                     std::string &err) {
     out.pattern = pattern;
     out.case_insensitive = case_insensitive;
     out.format = format;
     memset(&out.dev, 0, sizeof out.dev);
+    memset(&out.score, 0, sizeof out.score);
+    if (is_score_spec(pattern)) {   // (the reserved prefix: case_insensitive plays no part)
+        if (!vgf_is_hex((int)format)) {
+            err = "a score specification scores the hex digits of an address: ethereum, ethereum-contract and ethereum-create2 only";
+            return false;
+        }
+        if (!score_parse(pattern, out.score, err)) return false;
+        out.dev.kind = DEVF_SCORE;
+        score_odds(out.score, &out.selectivity, nullptr);
+        return true;
+    }
     if (!regex_compile(pattern, case_insensitive, out.dfa, err)) return false;
     if (out.dfa.lazy) {
         // no DFA tables (regex_dfa.h): nothing to derive a device test from — the reference's mode, every key to the host
@@ -909,6 +1051,11 @@ bool payload_from_address(uint32_t format, const std::string &address, uint8_t o
 
 void filter_which(const vgen_filter &f, const std::string &address, const uint8_t *payload, std::vector<uint32_t> &out) {
     out.clear();
+    if (f.score.n) {
+        bool ok = false;
+        if (score_of(f, address, payload, nullptr, &ok) && ok) out.push_back(0);
+        return;
+    }
     if (!f.list) {
         if (f.dfa.is_match(address)) out.push_back(0);
         return;
@@ -928,6 +1075,10 @@ void filter_which(const vgen_filter &f, const std::string &address, const uint8_
 }
 
 bool filter_accepts(const vgen_filter &f, const std::string &address, const uint8_t *payload) {
+    if (f.score.n) {
+        bool ok = false;
+        return score_of(f, address, payload, nullptr, &ok) && ok;
+    }
     if (!f.list) return f.dfa.is_match(address);
     std::vector<uint32_t> w;
     filter_which(f, address, payload, w);

@@ -56,6 +56,7 @@ struct vgen_filter {
     std::vector<uint32_t> chk_lut;   // Bech32 checksum tables (20 x 256) when the prefilter tests the checksum
     std::vector<uint32_t> dfa_blob;  // DEVF_DFA: the DFA in device layout (core/dfa_eval.h)
     std::shared_ptr<vg::PatternList> list;   // DEVF_LIST: the pattern list (dfa above stays empty)
+    vg::ScoreTerms score{};                  // DEVF_SCORE: the terms of a score specification (n = 0: not one; dfa stays empty)
 };
 
 namespace vg {
@@ -63,6 +64,23 @@ namespace vg {
 // Compiles pattern + derives the device prefilter for `format`. false + err on invalid patterns.
 bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t format, vgen_filter &out,
                     std::string &err);
+
+// Score specifications ("score:" + 1 - 4 terms `<metric>>=<n>` joined by '&'; metrics zero-bytes, leading-zero-bytes, leading:<h>,
+// count:<h> on the 40 hex digits of the address; include/vgen_hip.h).  The prefix is reserved: ':' is in no address alphabet, so
+// as a regular expression such a string could never match.  filter_compile takes one for the hex formats (device kind DEVF_SCORE).
+bool is_score_spec(const std::string &pattern);
+// ... on any other format it is VGEN_E_UNSUPPORTED, in vgen_filter_compile and in every scan alike
+inline bool score_spec_unsupported(const std::string &pattern, uint32_t format) { return is_score_spec(pattern) && !vgf_is_hex((int)format); }
+constexpr const char *SCORE_FORMATS_MESSAGE =
+    "a score specification scores the hex digits of an address: formats 5 (ethereum), 6 (ethereum-contract) and 7 (ethereum-create2) only";
+bool score_parse(const std::string &spec, ScoreTerms &out, std::string &err);
+// Fraction of uniformly random payloads a specification accepts, and its reciprocal rounded down (saturating): exact for one term
+// (binomial tail with (20, 1/256) or (40, 1/16); 256^-n or 16^-n for the leading runs).  For several terms the smallest single-term
+// probability: an UPPER bound on the hit rate, a LOWER bound on the difficulty.
+void score_odds(const ScoreTerms &s, double *selectivity, uint64_t *difficulty);
+// The score of `address` under a score filter (the value of the first term's metric); false when the filter is no score filter or
+// the string is no address of its format.  `payload` (optional) spares the decode.  *accepted: every term holds.
+bool score_of(const vgen_filter &f, const std::string &address, const uint8_t *payload, uint32_t *score, bool *accepted);
 
 // Hard limit on the patterns of one list (vgen_hip.h: vgen_filter_compile_list).
 constexpr uint32_t LIST_MAX_PATTERNS = 1u << 20;

@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include "../device/device_types.h"
+#include "filter.h"
 
 namespace vg {
 namespace {
@@ -133,6 +134,7 @@ const char *format_charset_name(unsigned format) {
 }
 
 std::string pattern_invalid_chars(const std::string &p, bool case_insensitive, unsigned format) {
+    if (is_score_spec(p)) return std::string();   // a score specification is no regular expression: nothing to flag
     const Alphabet alpha(alphabet_of(charset_of(format)), case_insensitive);
     OrderedChars bad;
     size_t i = 0;
@@ -166,6 +168,14 @@ unsigned pattern_fixed_chars(const std::string &p) {
 }
 
 uint64_t pattern_difficulty(const std::string &p, bool case_insensitive, unsigned format) {
+    if (is_score_spec(p)) {
+        // exact for one term; for several the largest single-term difficulty, a LOWER bound (filter.h: score_odds)
+        ScoreTerms terms;
+        std::string err;
+        uint64_t d = 1;
+        if (score_parse(p, terms, err)) score_odds(terms, nullptr, &d);
+        return d;
+    }
     const Charset cs = charset_of(format);
     const uint64_t alphabet = cs == Charset::Base58 ? (case_insensitive ? 34 : 58) : cs == Charset::Bech32 ? 32 : 16;
     unsigned fixed = pattern_fixed_chars(p);

@@ -23,6 +23,8 @@ unsigned pattern_fixed_chars(const std::string &pattern);
 
 // alphabet ^ (fixed characters - characters of the format's constant prefix when the pattern is
 // anchored on it), saturating at 2^64-1; 1 when nothing is fixed.
+// A score specification ("score:...", filter.h): the reciprocal of the fraction of payloads it accepts, rounded down — exact for
+// one term; for several terms the largest single-term value, which is a LOWER bound on the difficulty of the conjunction.
 uint64_t pattern_difficulty(const std::string &pattern, bool case_insensitive, unsigned format);
 
 }  // namespace vg

@@ -596,13 +596,18 @@ bool list_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind ==
 // The Ethereum-contract kernels only write payloads (kernels.hip: DumpOnly): a pattern's device filter runs behind them over
 // the frame's device-only payload buffer and the list path's compaction makes the records.
 // CREATE2 takes the same road for an on-device automaton (create2_kernel<DUMP>, then the automaton over the written payloads) ...
+// A score specification (DEVF_SCORE, hex formats) has kernels of its own: formats 5 and 6 dump into the frame's device-only buffer as for a
+// list and payload_score_kernel scores the slots; format 7 hashes and scores in create2_score_kernel.  The compaction follows either.
+bool score_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind == DEVF_SCORE; }
 bool deferred_filter(const vgen_ctx *c) {
     return (c->format == VGF_ETHEREUM_CONTRACT || (c->format == VGF_ETHEREUM_CREATE2 && c->h_filter.kind == DEVF_DFA)) && c->have_filter && !dump_mode(c) &&
-           !list_mode(c);
+           !list_mode(c) && !score_mode(c);
 }
 // ... and evaluates a prefilter (kinds 1 - 3) inside its own kernel: hit mask and the hits' payloads into the frame's list buffers,
 // then the compaction alone.
-bool inline_filter(const vgen_ctx *c) { return c->format == VGF_ETHEREUM_CREATE2 && c->have_filter && !dump_mode(c) && !list_mode(c) && !deferred_filter(c); }
+bool inline_filter(const vgen_ctx *c) {
+    return c->format == VGF_ETHEREUM_CREATE2 && c->have_filter && !dump_mode(c) && !list_mode(c) && !deferred_filter(c) && !score_mode(c);
+}
 
 // The pattern-list buffers of every frame: the payloads of a dispatch (20 B per key, x 6 on an endomorphism context, 32 B for
 // P2TR) and the hit mask (one bit per slot).  Device memory only — the payloads never leave the device — so, unlike dump mode,
@@ -655,7 +660,9 @@ int upload_ptab(vgen_ctx *c, const PatternList &L) {
 int enqueue_ptab(vgen_ctx *c, vgen_ctx::Frame &f, uint32_t count, bool endo) {
     PtabArgs p;
     memset(&p, 0, sizeof p);
-    if (deferred_filter(c)) {
+    if (score_mode(c)) {
+        // (the compaction reads nothing but the buffers, the ring and the geometry below)
+    } else if (deferred_filter(c)) {
         p.filter = c->d_filter;
         if (c->h_filter.kind == DEVF_DFA) {
             p.dfa_blob = c->h_filter.dfa_blob;
@@ -674,6 +681,19 @@ int enqueue_ptab(vgen_ctx *c, vgen_ctx::Frame &f, uint32_t count, bool endo) {
     p.images = endo ? 6 : 1;
     p.match_base = f.match_base;
     p.match_cap = c->match_cap;
+    if (score_mode(c)) {
+        if (c->score.n == 0) return c->fail(VGEN_E_STATE, "the context's score filter has no terms (vgen_set_filter installs them)");
+        ScoreArgs sa;
+        memset(&sa, 0, sizeof sa);
+        sa.terms = c->score;   // as they stand now: vgen_set_score_min changes later dispatches only
+        sa.payloads = f.d_list;
+        sa.hits = f.d_hits;
+        sa.stride = p.stride;
+        sa.count = p.count;
+        sa.images = p.images;
+        HIP_TRY(c, launch_payload_score(sa, p, f.s));
+        return VGEN_OK;
+    }
     HIP_TRY(c, launch_ptab(p, (int)c->payload_words, f.s));
     return VGEN_OK;
 }
@@ -686,9 +706,11 @@ int rt_set_filter(vgen_ctx *c, const vgen_filter *f) {
         if (fr.in_flight) return c->fail(VGEN_E_STATE, "vgen_set_filter while a dispatch is in flight");
     if (!f) {
         c->have_filter = false;
+        memset(&c->score, 0, sizeof c->score);
         return ensure_dump_slab(c);
     }
     if (f->format != c->format) return c->fail(VGEN_E_INVALID, "filter was compiled for another address format");
+    c->score = f->score;   // a score filter's terms (n = 0 for every other filter): what each dispatch copies into its kernel arguments
     if (f->list) {   // a pattern list: its table and the frames' payload buffers (the per-key kernels run as in dump mode)
         if (int rc = ensure_list_slab(c)) return rc;
         if (int rc = upload_ptab(c, *f->list)) return rc;
@@ -718,7 +740,7 @@ int rt_set_filter(vgen_ctx *c, const vgen_filter *f) {
     if (int rc = upload(c, c->d_filter, &c->h_filter, sizeof(DevFilter))) return rc;
     c->have_filter = true;
     if (dump_mode(c)) return ensure_dump_slab(c);
-    if (deferred_filter(c) || inline_filter(c)) return ensure_list_slab(c);
+    if (deferred_filter(c) || inline_filter(c) || score_mode(c)) return ensure_list_slab(c);
     return VGEN_OK;
 }
 
@@ -1257,7 +1279,7 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
     const bool endo_now = c->endo && !(a.dfa_bytes && parks_y && a.dfa_bytes + 2u * 9u * KEYS_WG * 4u > 64u * 1024u);
     a.endo = endo_now ? 1u : 0u;
     a.vstride = c->batch;
-    const bool listed = list_mode(c) || deferred_filter(c);
+    const bool listed = list_mode(c) || deferred_filter(c) || score_mode(c);
     if (dump) {
         if (int rc = ensure_dump_frame(c, (uint32_t)(&f - c->fr.data()))) return rc;
         if (n < c->batch) HIP_TRY(c, hipMemsetAsync(f.d_dump, 0, (size_t)c->batch * (endo_now ? 6 : 1) * c->payload_words * sizeof(uint32_t), f.s));
@@ -1353,7 +1375,7 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
         a.lone = others <= c->lone_max_others;
     }
     const bool dump = dump_mode(c);
-    const bool listed = list_mode(c) || deferred_filter(c);
+    const bool listed = list_mode(c) || deferred_filter(c) || score_mode(c);
     if (dump) {
         if (int rc = ensure_dump_frame(c, (uint32_t)(&f - c->fr.data()))) return rc;
         a.dump = f.d_dump;
@@ -1444,6 +1466,7 @@ static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter)
     a.first = first_counter;
     const bool dump = dump_mode(c);
     const bool inl = inline_filter(c);
+    const bool scored = score_mode(c);
     const bool listed = list_mode(c) || deferred_filter(c);
     PtabArgs p;
     memset(&p, 0, sizeof p);
@@ -1453,7 +1476,7 @@ static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter)
     } else {
         if (!f.d_list) return c->fail(VGEN_E_STATE, "the context's filter has no list buffers");   // (made by vgen_set_filter)
         a.payloads = f.d_list;
-        if (inl) {
+        if (inl || scored) {
             a.hits = f.d_hits;
             a.filter = c->d_filter;
             p.payloads = f.d_list;
@@ -1470,7 +1493,19 @@ static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter)
         HIP_TRY(c, hipEventRecord(f.ev_start, f.s));
         HIP_TRY(c, hipEventRecord(f.ev_mid, f.s));
     }
-    HIP_TRY(c, launch_create2(a, c->batch, inl ? &p : nullptr, f.s));
+    if (scored) {   // hash, score and the hit lanes' payloads in one kernel, then the compaction
+        if (c->score.n == 0) return c->fail(VGEN_E_STATE, "the context's score filter has no terms (vgen_set_filter installs them)");
+        Create2ScoreArgs sa;
+        memset(&sa, 0, sizeof sa);
+        sa.terms = c->score;
+        memcpy(sa.m, a.m, sizeof sa.m);
+        sa.first = a.first;
+        sa.hits = f.d_hits;
+        sa.out = f.d_list;
+        HIP_TRY(c, launch_create2_score(sa, c->batch, p, f.s));
+    } else {
+        HIP_TRY(c, launch_create2(a, c->batch, inl ? &p : nullptr, f.s));
+    }
     if (listed)
         if (int rc = enqueue_ptab(c, f, c->batch, false)) return rc;
     return finish_dispatch(c, f, dump, c->batch, false);

@@ -84,6 +84,9 @@ struct vgen_ctx {
     // scanner.cpp reach the CREATE2 job and dispatch through these, so the rt_* interface below stays what the stand-in implements
     int (*create2_set)(vgen_ctx *, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]) = nullptr;
     int (*create2_dispatch)(vgen_ctx *, uint32_t frame, uint64_t first_counter) = nullptr;
+    // DEVF_SCORE: the terms of the installed score filter (set by rt_set_filter, the first threshold replaced by vgen_set_score_min;
+    // n = 0 for every other filter and in dump mode).  Copied by value into each dispatch's kernel arguments.
+    vg::ScoreTerms score{};
     // DEVF_LIST: the list's interval table on the device (bitmap | offsets | lo | hi), and the frames' device-only payload
     // buffers + hit masks (made by vgen_set_filter when a list is first set: never on the dispatch path)
     uint8_t *d_ptab = nullptr;
@@ -186,6 +189,7 @@ int rt_create(const vgen_params *p, vgen_ctx **out, std::string &err);
 bool rt_prepare_streams(vgen_ctx *ctx);
 bool rt_frame_ready(vgen_ctx *ctx, uint32_t frame);
 void rt_destroy(vgen_ctx *ctx);
+// (installs ctx->score too: a score filter's terms, n = 0 for anything else; vgen_set_filter repeats that for runtimes that do not)
 int rt_set_filter(vgen_ctx *ctx, const vgen_filter *f);
 int rt_set_match_cap(vgen_ctx *ctx, uint32_t cap);
 int rt_dispatch(vgen_ctx *ctx, uint32_t frame, const uint8_t start_key_be[32]);

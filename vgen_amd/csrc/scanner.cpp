@@ -28,6 +28,7 @@
 #include "host/encode.h"
 #include "host/filter.h"
 #include "host/host_pool.h"
+#include "host/best_ledger.h"
 #include "host/list_ledger.h"
 #include "host/scalar.h"
 #include "host/scan_match.h"
@@ -124,10 +125,12 @@ struct ResultSink {
     uint32_t ck_slot = 0;
     SlotProgress *slot = nullptr;
     ListLedger *ll = nullptr;
+    BestLedger *best = nullptr;          // VGEN_SCAN_BEST: like a list's ledger, it decides in global batch order what is a result
 
     // does every candidate of a batch have to be examined?
-    bool examine_all() const { return ck != nullptr || ll != nullptr; }
+    bool examine_all() const { return ck != nullptr || ll != nullptr || best != nullptr; }
     uint64_t found() const {
+        if (best) return best->n_accepted.load(std::memory_order_relaxed);
         if (ll) return ll->n_accepted.load(std::memory_order_relaxed);
         return shared_found ? shared_found->load(std::memory_order_relaxed) : matches.size();
     }
@@ -139,7 +142,7 @@ struct ResultSink {
     // is there a reason to examine another candidate of the batch in hand?
     bool wants_more() const { return examine_all() || room() > 0; }
     // the scan has what it was asked for (a pattern-list scan: when its ledger says so — every pattern has its matches, or `count`)
-    bool done() const { return ll ? ll->done.load(std::memory_order_relaxed) : found() >= count; }
+    bool done() const { return best ? best->done.load(std::memory_order_relaxed) : ll ? ll->done.load(std::memory_order_relaxed) : found() >= count; }
     // batches of this slot that are finished already: recorded in the checkpoint, or committed by the context that owned
     // the slot before it failed; and those of them that count against max_batches (the slot's budget; a checkpoint's is per call)
     uint64_t batches_done() const { return ck ? ck->done[ck_slot] : slot ? slot->done.load() : 0; }
@@ -149,7 +152,7 @@ struct ResultSink {
     // batch's record when there is one.
     void add(const LiteMatch &g) {
         if (examine_all()) batch.push_back(g);
-        if (ll || room() == 0) return;
+        if (ll || best || room() == 0) return;
         matches.push_back(g);
         taken_uncommitted++;
         if (shared_found) shared_found->fetch_add(1, std::memory_order_relaxed);
@@ -159,7 +162,7 @@ struct ResultSink {
     bool add_parts(std::vector<std::vector<LiteMatch>> &part) {
         size_t total = 0;
         for (auto &p : part) total += p.size();
-        size_t take = ll ? 0 : (size_t)std::min<uint64_t>(total, room());
+        size_t take = ll || best ? 0 : (size_t)std::min<uint64_t>(total, room());
         const size_t taken = take;
         for (auto &p : part) {
             if (examine_all()) batch.insert(batch.end(), p.begin(), p.end());
@@ -175,6 +178,7 @@ struct ResultSink {
     void commit(uint64_t batch_no, uint64_t tested) {
         if (ck) ck->commit(ck_slot, batch, tested);
         if (ll) ll->submit(batch_no, std::move(batch));
+        if (best) best->submit(batch_no, std::move(batch));
         batch.clear();
         if (slot) slot->done.fetch_add(1);
         taken_uncommitted = 0;
@@ -279,6 +283,16 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
     }
     int rc = vgen_set_filter(ctx, host_all ? nullptr : &flt);
     if (rc != VGEN_OK) return rc;
+    // VGEN_SCAN_BEST: the device's threshold follows the best score so far (a context that joins or takes a slot over starts from it).
+    // An optimisation only: the ledger applies the rule, and dispatches in flight under an older threshold deliver extras it discards.
+    int64_t best_sent = -1;
+    auto follow_best = [&]() {
+        if (!sink.best || host_all || !ctx->have_filter) return;
+        const int64_t b = sink.best->best.load(std::memory_order_relaxed);
+        if (b <= best_sent || b + 1 > (int64_t)sink.best->max_score() || (uint32_t)(b + 1) <= flt.score.t[0].min) return;
+        if (vgen_set_score_min(ctx, (uint32_t)(b + 1)) == VGEN_OK) best_sent = b;
+    };
+    follow_best();
 
     // Scans that multiply a scalar per key (random keys, taproot): how wide a generator table is this scan worth?  The default
     // 24-bit table (10 additions per multiplication) is there in 30 ms; the 27-bit signed one (9 additions, +5 %) in 60 ms and
@@ -548,6 +562,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
         total_ops += tested;                         // gpu.rs:1106 (batch_size; six times that for an endomorphism dispatch)
         cut_any = cut_any || cut;
         sink.commit(batch_start.batch_no * shards + shard, tested);
+        follow_best();
         if (job.cb) job.cb(job.shared_ops ? tested : total_ops, job.user);   // multi-device: the wrapper adds N to the shared count under its lock
         if (sink.done() && !dispatched_next) break;   // gpu.rs:1111
         if (table_path && !upgrade_asked && std::chrono::duration<double>(std::chrono::steady_clock::now() - scan_t0).count() >= 5.0) {
@@ -681,6 +696,14 @@ static bool normalise_scan_config(const vgen_scan_config *in, vgen_scan_config &
     return true;
 }
 
+// VGEN_SCAN_BEST is for score specifications, and not for checkpointed scans (the rule needs the scores of everything reported before).
+static int check_best(vgen_ctx *ctx, const vgen_scan_config &c, const vgen_filter &flt) {
+    if (!(c.flags & VGEN_SCAN_BEST)) return VGEN_OK;
+    if (flt.score.n == 0) return ctx->fail(VGEN_E_INVALID, "the scan flag `best` (vgen_scan_config.flags = 2) needs a score specification ('score:...') as the pattern");
+    if (c.checkpoint_path) return ctx->fail(VGEN_E_UNSUPPORTED, "the scan flag `best` (vgen_scan_config.flags = 2) together with checkpoint_path is not supported: a resumed scan would not know the scores reported before");
+    return VGEN_OK;
+}
+
 extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_config *cfg_in, vgen_progress_cb cb,
                          void *user, const volatile int32_t *stop, vgen_scan_result *out) {
     vgen_scan_config c;   // (a checkpoint may give it the file's base key)
@@ -690,14 +713,22 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
     const auto t0 = std::chrono::steady_clock::now();
     vgen_filter flt;
     std::string err;
+    if (score_spec_unsupported(pattern, c.format)) return ctx->fail(VGEN_E_UNSUPPORTED, SCORE_FORMATS_MESSAGE);
     if (!filter_compile(pattern, c.case_insensitive != 0, c.format, flt, err))
         return ctx->fail(VGEN_E_PATTERN, err);
     // One flow, with or without a checkpoint.  With one, what earlier runs found counts towards `count` (committed batches keep
     // all their matches), and nothing is dispatched when the file says the scan is complete or already holds `count` matches.
     // While the shard runs, its matches stay the first `count` of the checkpoint's record: they serve every way out.
+    if (int rc = check_best(ctx, c, flt)) return rc;
     std::unique_ptr<Checkpoint> ck;
     RndSeed rnd_seed{};
     ResultSink sink(c.count);
+    BestLedger bl;
+    if (c.flags & VGEN_SCAN_BEST) {
+        bl.init(&flt, c.count);
+        bl.arrival = true;   // one context: its batches are committed in the scan's order (whatever stripe of a sharding it walks)
+        sink.best = &bl;
+    }
     if (c.checkpoint_path) {
         ck.reset(new Checkpoint);
         const uint32_t shards = c.n_shards > 1 ? c.n_shards : 1;
@@ -725,6 +756,7 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
     // runs included — the file holds the same): a host that falls back to another backend (the reference's run_search does,
     // src/lib.rs:727-746,1185-1198) keeps those matches
     const std::string why = ctx->err;
+    if (sink.best) sink.matches.take(std::vector<LiteMatch>(bl.accepted), bl.accepted.size());
     const int frc = finish_result(ctx, c.format, sink.matches, job.operations, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
     if (rc != VGEN_OK) {
         out->failed_shards = 1;
@@ -742,6 +774,9 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
 // the shards hand their confirmed matches to the list's ledger, which decides what the scan returns.
 static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &flt, const char *pattern, const vgen_scan_config *cfg,
                           vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out, ListLedger *ll) {
+    if (int rc = check_best(ctxs[0], *cfg, flt)) return rc;
+    BestLedger best_ledger;
+    BestLedger *bl = (cfg->flags & VGEN_SCAN_BEST) ? &best_ledger : nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     vgen_scan_config base = *cfg;
     Checkpoint ck;
@@ -760,6 +795,10 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
     // the walk of an endomorphism context starts from a random base of its own per device; random-key scans stripe by
     // stream (shard i walks stream i) whatever the context
     const bool own_bases = endo && !random_keys;   // no slots to stripe or adopt: every context walks from its own random base
+    if (bl) {
+        bl->init(&flt, cfg->count);
+        bl->arrival = own_bases && n_ctx > 1;
+    }
     RndSeed rnd_seed{};   // random-key scans: one seed for all streams (shard i walks stream i of it)
     if (cfg->checkpoint_path) {
         int rc = open_checkpoint(ctxs[0], ck, pattern, base, ctxs[0]->batch, n_ctx, 0, n_ctx, rnd_seed);
@@ -807,7 +846,8 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
         c->cb(c->ops->fetch_add(delta) + delta, c->user);
     };
     auto scan_over = [&]() {
-        return (stop && __atomic_load_n(const_cast<const int32_t *>(stop), __ATOMIC_RELAXED) != 0) || (ll ? ll->done.load() : found.load() >= cfg->count);
+        return (stop && __atomic_load_n(const_cast<const int32_t *>(stop), __ATOMIC_RELAXED) != 0) ||
+               (bl ? bl->done.load() : ll ? ll->done.load() : found.load() >= cfg->count);
     };
     std::vector<std::thread> th;
     for (uint32_t i = 0; i < n_ctx && !skip_all; i++)
@@ -829,6 +869,7 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
                 sink.ck_slot = slot;
                 sink.slot = own_bases ? nullptr : &progress[slot];
                 sink.ll = ll;
+                sink.best = bl;
                 const int rc = scan_shard(ctxs[i], flt, job, sink);
                 std::unique_lock<std::mutex> lk(q_mu);
                 part[slot].append(std::move(sink.matches));
@@ -885,7 +926,10 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
     // The results: a list's are its ledger's, in the scan's order; else what the checkpoint recorded (earlier runs' matches +
     // every batch committed by this one) or what the shards took, in ascending key order
     std::vector<LiteMatch> all;
-    if (ll) {
+    if (bl) {
+        bl->flush();
+        all = bl->accepted;
+    } else if (ll) {
         ll->flush();
         all = ll->accepted;
     } else if (ckp) {
@@ -896,7 +940,7 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
             all.insert(all.end(), flat.begin(), flat.end());
         }
     }
-    if (!ll) std::sort(all.begin(), all.end(), [](const LiteMatch &a, const LiteMatch &b) { return memcmp(a.key, b.key, 32) < 0; });
+    if (!ll && !bl) std::sort(all.begin(), all.end(), [](const LiteMatch &a, const LiteMatch &b) { return memcmp(a.key, b.key, 32) < 0; });
     uint64_t total = 0;
     for (uint64_t o : ops) total += o;
     MatchList result;
@@ -930,6 +974,7 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
     const vgen_scan_config *cfg = &cfg_full;
     vgen_filter flt;
     std::string err;
+    if (score_spec_unsupported(pattern, cfg->format)) return ctxs[0]->fail(VGEN_E_UNSUPPORTED, SCORE_FORMATS_MESSAGE);
     if (!filter_compile(pattern, cfg->case_insensitive != 0, cfg->format, flt, err))
         return ctxs[0]->fail(VGEN_E_PATTERN, err);
     return scan_multi_run(ctxs, n_ctx, flt, pattern, cfg, cb, user, stop, out, nullptr);
@@ -990,12 +1035,16 @@ extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pa
         for (auto &f : ctxs[i]->fr)
             if (f.in_flight) return c0->fail(VGEN_E_STATE, "vgen_scan_create2 while a dispatch is in flight");
     }
-    if (c.has_start || c.has_end || c.seed || c.shard || c.n_shards > 1 || c.checkpoint_path || c.flags)
-        return c0->fail(VGEN_E_UNSUPPORTED, "vgen_scan_create2 reads format, count, case_insensitive and max_batches: start / end, seed, shards, checkpoints and flags do not apply to a salt search");
+    if ((c.flags & VGEN_SCAN_BEST) && c.checkpoint_path)
+        return c0->fail(VGEN_E_UNSUPPORTED, "the scan flag `best` (vgen_scan_config.flags = 2) together with checkpoint_path is not supported: a resumed scan would not know the scores reported before");
+    if (c.has_start || c.has_end || c.seed || c.shard || c.n_shards > 1 || c.checkpoint_path || (c.flags & ~VGEN_SCAN_BEST))
+        return c0->fail(VGEN_E_UNSUPPORTED, "vgen_scan_create2 reads format, count, case_insensitive, max_batches and the scan flag `best` (2): start / end, seed, shards, checkpoints and other flags do not apply to a salt search");
     const auto t0 = std::chrono::steady_clock::now();
     vgen_filter flt;
     std::string err;
+    if (score_spec_unsupported(pattern, c.format)) return c0->fail(VGEN_E_UNSUPPORTED, SCORE_FORMATS_MESSAGE);
     if (!filter_compile(pattern, c.case_insensitive != 0, c.format, flt, err)) return c0->fail(VGEN_E_PATTERN, err);
+    if (int brc = check_best(c0, c, flt)) return brc;
     const bool dump = flt.dev.kind == DEVF_HOST_ALL;   // no device filter: every payload comes back and the host filters
     const uint32_t batch = c0->batch;
     // whole batches the counter space holds from first_counter on (a tail shorter than a batch is not tested)
@@ -1008,7 +1057,7 @@ extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pa
         l.next = i;
         l.nframes = l.ctx->frames;
         if ((rc = rt_set_create2(l.ctx, deployer, init_code_hash, salt_prefix)) != VGEN_OK) break;
-        if ((rc = rt_set_filter(l.ctx, &flt)) != VGEN_OK) break;
+        if ((rc = vgen_set_filter(l.ctx, &flt)) != VGEN_OK) break;   // (through the C entry point: it also installs a score filter's terms)
         if (dump) {
             uint32_t df = 0;
             if ((rc = rt_get_resources(l.ctx, &df, nullptr, nullptr, nullptr)) != VGEN_OK) break;
@@ -1021,6 +1070,12 @@ extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pa
     }
     auto stopped = [&]() { return stop && __atomic_load_n(const_cast<const int32_t *>(stop), __ATOMIC_RELAXED) != 0; };
     ResultSink sink(c.count);
+    BestLedger bl;
+    int64_t best_sent = -1;   // VGEN_SCAN_BEST: the best score the contexts' thresholds follow
+    if (c.flags & VGEN_SCAN_BEST) {
+        bl.init(&flt, c.count);
+        sink.best = &bl;
+    }
     std::vector<vgen_match> recs;
     uint64_t ops = 0, g = 0;   // g: the next global batch to finish
     bool complete = false;
@@ -1086,12 +1141,19 @@ extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pa
             sink.add(m);
         }
         sink.commit(g, tested);
+        if (sink.best && bl.best.load() > best_sent && bl.best.load() + 1 <= (int64_t)bl.max_score()) {
+            // an improvement: later dispatches of every context report only what beats it (those in flight still deliver extras, discarded above)
+            best_sent = bl.best.load();
+            if ((uint32_t)(best_sent + 1) > flt.score.t[0].min)
+                for (auto &ln : lanes) (void)vgen_set_score_min(ln.ctx, (uint32_t)(best_sent + 1));
+        }
         ops += tested;
         g++;
         if (cb) cb(ops, user);
     }
     for (auto &l : lanes) create2_drain(l);
     const std::string why = failed ? failed->err : std::string();
+    if (sink.best) sink.matches.take(std::vector<LiteMatch>(bl.accepted), bl.accepted.size());
     out->n_matches = sink.matches.size();
     out->operations = ops;
     if (!sink.matches.empty()) {
