@@ -409,6 +409,31 @@ int vgen_set_create2(vgen_ctx *ctx, const uint8_t deployer[20], const uint8_t in
  * candidate, so the all-zero address (probability 2^-160) is not reported by them. */
 int vgen_dispatch_create2(vgen_ctx *ctx, uint32_t frame, uint64_t first_counter);
 
+/* ---- CREATE3: one address on every chain, by salt (a second kind of job on a VGEN_FMT_ETHEREUM_CREATE2 context) -------------
+ * A CREATE3 factory (Solmate / Solady CREATE3, CreateX, ZeframLou's create3-factory) deploys a fixed 16-byte proxy with CREATE2 and
+ * lets that proxy deploy the contract with CREATE, nonce 1, so the address does not depend on the contract's init code:
+ *     proxy    = keccak256(0xff || factory || salt' || proxy_init_code_hash)[12..32]
+ *     contract = keccak256(0xd6 0x94 || proxy || 0x01)[12..32]
+ * salt' is the caller's salt itself (no guard, guard_len = -1) or keccak256(guard || salt) with a guard of 0 .. 64 bytes - e.g. the
+ * 20 bytes of msg.sender (ZeframLou), the sender ABI-padded to 32 bytes, sender and chain id (64 bytes) or nothing: a guard of
+ * length 0 hashes the salt alone and is NOT the same as no guard.  The library knows no factory's rules: the caller composes the
+ * guard bytes.  A job is (factory, proxy_init_code_hash, salt_prefix[24], guard); candidate `counter` has the RAW salt
+ * salt_prefix || u64be(counter), as for CREATE2, and that raw salt is what the caller passes to the factory.  The device runs two
+ * Keccak blocks per salt, three with a guard.  No new format: results carry format 7, the payload is the contract's 20 bytes. */
+/* keccak256 of the proxy 67363d3d37363d34f03d5260086018f3 that Solmate / Solady and CreateX deploy: the usual proxy_init_code_hash. */
+int vgen_create3_proxy_hash(uint8_t out[32]);
+/* The contract's address for one raw salt, and the proxy's when proxy_out is not NULL.  guard_len -1: no guard; 0 .. 64: hashed,
+ * and guard may be NULL only when guard_len <= 0; any other guard_len is VGEN_E_INVALID. */
+int vgen_create3_address(const uint8_t factory[20], const uint8_t salt[32], const uint8_t proxy_init_code_hash[32], const uint8_t *guard,
+                         int32_t guard_len, uint8_t proxy_out[20], uint8_t out[20]);
+/* Installs a CREATE3 job on a VGEN_FMT_ETHEREUM_CREATE2 context; statuses as for vgen_set_create2 (VGEN_E_INVALID on any other
+ * context or a bad guard_len, VGEN_E_STATE while something is in flight).  It replaces a CREATE2 job and vgen_set_create2 replaces
+ * it; vgen_dispatch_create2 dispatches whichever job is installed, its contract otherwise unchanged (index i is counter
+ * first_counter + i; the range check, dumps, filters, lists, automata, scores, match cap and timers as above - and the same
+ * known limitation: lists and on-device automata never report the all-zero address). */
+int vgen_set_create3(vgen_ctx *ctx, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
+                     const uint8_t *guard, int32_t guard_len);
+
 /* ---- provider patterns (src/provider.rs) -------------------------------------------------------------- */
 
 /* provider::resolve (src/provider.rs:12-52): "boha:b1000:66" / "boha:b1000/66" -> the puzzle's target
@@ -553,6 +578,12 @@ int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter *list, uin
 int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const uint8_t deployer[20], const uint8_t init_code_hash[32],
                       const uint8_t salt_prefix[24], uint64_t first_counter, const vgen_scan_config *cfg, vgen_progress_cb cb, void *user,
                       const volatile int32_t *stop, vgen_scan_result *out);
+/* vgen_scan_create2 over a CREATE3 job (vgen_set_create3 on every context): the same rules, VGEN_SCAN_BEST and every refusal
+ * included.  In a result: address = the contract's EIP-55 address, key = the 32-byte RAW salt (what the factory is called with),
+ * hex = wif = its "0x" form, format = 7; the proxy and the guarded salt of a result come from vgen_create3_address / vgen_keccak256. */
+int vgen_scan_create3(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32],
+                      const uint8_t salt_prefix[24], const uint8_t *guard, int32_t guard_len, uint64_t first_counter,
+                      const vgen_scan_config *cfg, vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out);
 void vgen_scan_result_free(vgen_scan_result *r);
 
 #ifdef __cplusplus

@@ -157,6 +157,12 @@ _L.vgen_set_score_min.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
 _L.vgen_scan_create2.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                  ctypes.c_uint64, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32),
                                  ctypes.POINTER(_ScanResult)]
+_L.vgen_create3_proxy_hash.argtypes = [ctypes.c_char_p]
+_L.vgen_create3_address.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_char_p]
+_L.vgen_set_create3.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int32]
+_L.vgen_scan_create3.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+                                 ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p,
+                                 ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_ScanResult)]
 _L.vgen_device_name.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
 _L.vgen_scan.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p,
                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_ScanResult)]
@@ -304,6 +310,68 @@ class Create2Job:
 
     def address(self, counter: int) -> bytes:
         return create2_address(self.deployer, self.salt(counter), self.init_code_hash)
+
+
+def _guard_args(guard):
+    """(pointer, length) of an optional guard for the C ABI: None is no guard (-1), b"" the guard of length 0."""
+    if guard is None:
+        return None, -1
+    if isinstance(guard, str):
+        guard = bytes.fromhex(guard[2:] if guard[:2] in ("0x", "0X") else guard)
+    guard = bytes(guard)
+    if len(guard) > 64:
+        raise ValueError("guard is at most 64 bytes")
+    return guard, len(guard)
+
+
+def create3_proxy_hash() -> bytes:
+    """vgen_create3_proxy_hash: keccak256 of the 16-byte proxy that Solmate / Solady CREATE3 and CreateX deploy."""
+    out = ctypes.create_string_buffer(32)
+    _check(_L.vgen_create3_proxy_hash(out))
+    return out.raw
+
+
+def create3_address(factory, salt, proxy_init_code_hash=None, guard=None, with_proxy=False):
+    """vgen_create3_address: the address of the contract a CREATE3 factory deploys for the raw `salt`; guard=None is no guard, bytes
+    (0 to 64 of them) are hashed in front of the salt.  with_proxy=True returns (proxy, contract)."""
+    g, n = _guard_args(guard)
+    h = create3_proxy_hash() if proxy_init_code_hash is None else _hexbytes(proxy_init_code_hash, 32, "proxy_init_code_hash")
+    proxy, out = ctypes.create_string_buffer(20), ctypes.create_string_buffer(20)
+    _check(_L.vgen_create3_address(_hexbytes(factory, 20, "factory"), _hexbytes(salt, 32, "salt"), h, g, n, proxy, out))
+    return (proxy.raw, out.raw) if with_proxy else out.raw
+
+
+class Create3Job:
+    """What a CREATE3 salt search is about: the `factory`, the hash of the proxy it deploys (None: the usual proxy's), the caller's
+    part of the raw salt (up to 24 bytes, left-aligned, zero padded) and the guard the factory hashes in front of the salt
+    (None: the factory uses the raw salt; b"": keccak256(salt); e.g. the 20 bytes of msg.sender for ZeframLou's factory).
+    Candidate `counter` is the raw salt salt_prefix || counter as 8 big-endian bytes: what the factory is called with."""
+
+    def __init__(self, factory, proxy_init_code_hash=None, salt_prefix=b"", guard=None):
+        self.factory = _hexbytes(factory, 20, "factory")
+        self.proxy_init_code_hash = create3_proxy_hash() if proxy_init_code_hash is None else _hexbytes(proxy_init_code_hash, 32, "proxy_init_code_hash")
+        if isinstance(salt_prefix, str):
+            salt_prefix = bytes.fromhex(salt_prefix[2:] if salt_prefix[:2] in ("0x", "0X") else salt_prefix)
+        if len(salt_prefix) > 24:
+            raise ValueError("salt_prefix is at most 24 bytes")
+        self.salt_prefix = bytes(salt_prefix).ljust(24, b"\0")
+        self.guard, self.guard_len = _guard_args(guard)
+
+    def salt(self, counter: int) -> bytes:
+        """The raw salt (vgen_create2_salt)."""
+        out = ctypes.create_string_buffer(32)
+        _check(_L.vgen_create2_salt(self.salt_prefix, counter, out))
+        return out.raw
+
+    def guarded_salt(self, counter: int) -> bytes:
+        """The salt the proxy is deployed under: keccak256(guard || salt), or the raw salt without a guard."""
+        return self.salt(counter) if self.guard is None else keccak256(self.guard + self.salt(counter))
+
+    def proxy(self, counter: int) -> bytes:
+        return create3_address(self.factory, self.salt(counter), self.proxy_init_code_hash, self.guard, with_proxy=True)[0]
+
+    def address(self, counter: int) -> bytes:
+        return create3_address(self.factory, self.salt(counter), self.proxy_init_code_hash, self.guard)
 
 
 @dataclass
@@ -573,6 +641,10 @@ class GpuRunner:
         """vgen_set_score_min: the first term's threshold of the installed score filter, for dispatches enqueued from now on."""
         _check(_L.vgen_set_score_min(self._h, minimum), self._h)
 
+    def set_create3(self, job: "Create3Job"):
+        """vgen_set_create3: a CREATE3 job on an EthereumCreate2 runner; dispatch_create2 then tests its salts."""
+        _check(_L.vgen_set_create3(self._h, job.factory, job.proxy_init_code_hash, job.salt_prefix, job.guard, job.guard_len), self._h)
+
     def dispatch_create2(self, first_counter: int, frame: int):
         """vgen_dispatch_create2: salts first_counter .. first_counter + batch_size - 1 of the job; results as for dispatch()."""
         _check(_L.vgen_dispatch_create2(self._h, frame, first_counter), self._h)
@@ -732,19 +804,14 @@ def scan_gpu_with_runner(pattern: str, config: ScanConfig, runner,
     return out
 
 
-def scan_create2(pattern: str, job: Create2Job, config: ScanConfig, runner, first_counter: int = 0,
-                 progress_cb: Optional[Callable[[int], None]] = None, stop=None) -> ScanResult:
-    """vgen_scan_create2: the salts of `job` from counter `first_counter` on, over one EthereumCreate2 GpuRunner or a list of them.
-    In a match, `hex` (and `wif`) is "0x" + the 32-byte salt; the address exists only when job.deployer executes CREATE2 with that
-    salt and the job's init code."""
+def _salt_scan(call, pattern, config, runner, progress_cb, stop) -> ScanResult:
     runners = list(runner) if isinstance(runner, (list, tuple)) else [runner]
     c = _scan_config(config)
     res = _ScanResult()
     cb = _PROGRESS(lambda ops, _u: progress_cb(ops)) if progress_cb else ctypes.cast(None, _PROGRESS)
     stop_p = ctypes.byref(stop) if stop is not None else None
     arr = (ctypes.c_void_p * len(runners))(*[r._h for r in runners])
-    rc = _L.vgen_scan_create2(arr, len(runners), pattern.encode(), job.deployer, job.init_code_hash, job.salt_prefix, first_counter,
-                              ctypes.byref(c), cb, None, stop_p, ctypes.byref(res))
+    rc = call(arr, len(runners), pattern.encode(), ctypes.byref(c), cb, stop_p, ctypes.byref(res))
     out = ScanResult(operations=res.operations, elapsed_secs=res.elapsed_secs, complete=bool(res.complete), failed_shards=res.failed_shards)
     for i in range(res.n_matches):
         g = res.matches[i]
@@ -756,3 +823,22 @@ def scan_create2(pattern: str, job: Create2Job, config: ScanConfig, runner, firs
         err.partial = out
         raise err
     return out
+
+
+def scan_create2(pattern: str, job: Create2Job, config: ScanConfig, runner, first_counter: int = 0,
+                 progress_cb: Optional[Callable[[int], None]] = None, stop=None) -> ScanResult:
+    """vgen_scan_create2: the salts of `job` from counter `first_counter` on, over one EthereumCreate2 GpuRunner or a list of them.
+    In a match, `hex` (and `wif`) is "0x" + the 32-byte salt; the address exists only when job.deployer executes CREATE2 with that
+    salt and the job's init code."""
+    return _salt_scan(lambda arr, n, pat, c, cb, stop_p, res: _L.vgen_scan_create2(arr, n, pat, job.deployer, job.init_code_hash, job.salt_prefix,
+                                                                                  first_counter, c, cb, None, stop_p, res),
+                      pattern, config, runner, progress_cb, stop)
+
+
+def scan_create3(pattern: str, job: Create3Job, config: ScanConfig, runner, first_counter: int = 0,
+                 progress_cb: Optional[Callable[[int], None]] = None, stop=None) -> ScanResult:
+    """vgen_scan_create3: the same search over a CREATE3 job.  In a match, `hex` (and `wif`) is "0x" + the 32-byte RAW salt, the one
+    job.factory is called with; job.proxy(counter) and job.guarded_salt(counter) give the rest."""
+    return _salt_scan(lambda arr, n, pat, c, cb, stop_p, res: _L.vgen_scan_create3(arr, n, pat, job.factory, job.proxy_init_code_hash, job.salt_prefix,
+                                                                                  job.guard, job.guard_len, first_counter, c, cb, None, stop_p, res),
+                      pattern, config, runner, progress_cb, stop)

@@ -426,4 +426,31 @@ int vgen_dispatch_create2(vgen_ctx *ctx, uint32_t frame, uint64_t first_counter)
     return vg::rt_dispatch_create2(ctx, frame, first_counter);
 }
 
+int vgen_create3_proxy_hash(uint8_t out[32]) {
+    if (!out) return VGEN_E_INVALID;
+    // the 16-byte proxy Solmate / Solady CREATE3 and CreateX deploy; hashed here, not stored
+    static const uint8_t proxy[16] = {0x67, 0x36, 0x3d, 0x3d, 0x37, 0x36, 0x3d, 0x34, 0xf0, 0x3d, 0x52, 0x60, 0x08, 0x60, 0x18, 0xf3};
+    vg::host_keccak256(proxy, sizeof proxy, out);
+    return VGEN_OK;
+}
+
+int vgen_create3_address(const uint8_t factory[20], const uint8_t salt[32], const uint8_t proxy_init_code_hash[32], const uint8_t *guard,
+                         int32_t guard_len, uint8_t proxy_out[20], uint8_t out[20]) {
+    if (!factory || !salt || !proxy_init_code_hash || !out || guard_len < -1 || guard_len > 64 || (guard_len > 0 && !guard)) return VGEN_E_INVALID;
+    // through the single-source twins of the device blocks and the message builders the kernels use (core/hash.h)
+    vg::u32 proxy[5], a[5];
+    vg::create3_address(factory, salt, proxy_init_code_hash, guard, guard_len, proxy, a);
+    if (proxy_out) memcpy(proxy_out, proxy, 20);
+    memcpy(out, a, 20);
+    return VGEN_OK;
+}
+
+int vgen_set_create3(vgen_ctx *ctx, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
+                     const uint8_t *guard, int32_t guard_len) {
+    if (!ctx) return VGEN_E_INVALID;
+    if (!factory || !proxy_init_code_hash || !salt_prefix) return ctx->fail(VGEN_E_INVALID, "vgen_set_create3: null job field");
+    if (guard_len < -1 || guard_len > 64 || (guard_len > 0 && !guard)) return ctx->fail(VGEN_E_INVALID, "vgen_set_create3: guard_len is -1 (no guard) or 0 .. 64 bytes");
+    return vg::rt_set_create3(ctx, factory, proxy_init_code_hash, salt_prefix, guard, guard_len);
+}
+
 }  // extern "C"

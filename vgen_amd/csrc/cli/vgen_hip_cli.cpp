@@ -49,6 +49,11 @@ struct Opts {
     // -f ethereum-create2: the job of the salt search
     std::string deployer, init_code_hash, init_code_file, salt_prefix, salt_start;
     bool has_deployer = false, has_init_code_hash = false, has_init_code_file = false, has_salt_prefix = false, has_salt_start = false;
+    // -f ethereum-create3: the same salt search through a CREATE3 factory (--deployer is the factory)
+    std::string proxy_hash, salt_guard;
+    bool has_proxy_hash = false, has_salt_guard = false, salt_guard_hash = false;
+    bool create3() const { return format == "ethereum-create3"; }
+    bool any_create3_option() const { return has_proxy_hash || has_salt_guard || salt_guard_hash; }
     bool any_create2_option() const { return has_deployer || has_init_code_hash || has_init_code_file || has_salt_prefix || has_salt_start; }
 };
 
@@ -65,8 +70,9 @@ int format_id(const std::string &f) {
     if (f == "ethereum") return VGEN_FMT_ETHEREUM;
     if (f == "ethereum-contract") return VGEN_FMT_ETHEREUM_CONTRACT;
     if (f == "ethereum-create2") return VGEN_FMT_ETHEREUM_CREATE2;
+    if (f == "ethereum-create3") return VGEN_FMT_ETHEREUM_CREATE2;   // no format of its own: a CREATE3 job on a format-7 context (Opts::create3)
     if (f == "p2pkh-uncompressed") return VGEN_FMT_P2PKH_UNCOMPRESSED;
-    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2)");
+    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2, ethereum-create3)");
 }
 
 const char *format_display(int id) {   // Display for AddressFormat, src/address.rs:48-58
@@ -220,6 +226,10 @@ void usage() {
             "                    four terms METRIC>=N with the metrics zero-bytes, leading-zero-bytes, leading:H and count:H (H a hex digit);\n"
             "                    results carry a score, the value of the first term's metric.  --best reports only results that beat every\n"
             "                    score before them, -c then bounds the number of improvements.  range and estimate take such a pattern too)\n"
+            "  vgen-hip generate -f ethereum-create3 -p PATTERN --deployer 0xFACTORY [--proxy-init-code-hash 0xHASH] [--salt-guard 0xHEX | --salt-guard-hash]\n"
+            "                    [--salt-prefix 0xHEX] [--salt-start N] [-c COUNT] [-i] [--devices ..] [-o ..]   (CREATE3: the contract the factory's\n"
+            "                    proxy deploys, whatever its init code; searches the RAW salt as above.  --salt-guard: the 0 - 64 bytes the factory\n"
+            "                    hashes in front of the salt, e.g. the sender's 20 bytes; --salt-guard-hash: it hashes the salt alone)\n"
             "  vgen-hip generate --patterns-file FILE [--per-pattern N] ...   (instead of -p: one start-anchored prefix per line,\n"
             "                    one scan; N results per pattern (default 1, 0 = unbounded), -c caps the total (default: none);\n"
             "                    each result's pattern field is the lowest-index line it satisfies.  range takes it too)\n"
@@ -244,7 +254,7 @@ Opts parse(int argc, char **argv) {
                                                   "--seed", "--devices", "--frames", "--checkpoint", "--range", "--puzzle", "--key", "--address",
                                                   "--prefix-length", "--provider-table", "--threads", "--backend", "--cpu-batch-size", "--table-bits-max",
                                                   "--mem-budget-gib", "--patterns-file", "--per-pattern", "--deployer", "--init-code-hash", "--init-code-file",
-                                                  "--salt-prefix", "--salt-start"};
+                                                  "--salt-prefix", "--salt-start", "--proxy-init-code-hash", "--salt-guard"};
     static const char short_with_value[] = "pfcorkaltT";
     std::vector<std::string> args;
     bool next_is_value = false;
@@ -320,6 +330,9 @@ Opts parse(int argc, char **argv) {
         else if (a == "--init-code-file") { o.init_code_file = val(); o.has_init_code_file = true; }
         else if (a == "--salt-prefix") { o.salt_prefix = val(); o.has_salt_prefix = true; }
         else if (a == "--salt-start") { o.salt_start = val(); o.has_salt_start = true; }
+        else if (a == "--proxy-init-code-hash") { o.proxy_hash = val(); o.has_proxy_hash = true; }
+        else if (a == "--salt-guard") { o.salt_guard = val(); o.has_salt_guard = true; }
+        else if (a == "--salt-guard-hash") o.salt_guard_hash = true;
         else if (a == "-t" || a == "--threads" || a == "--backend" || a == "--cpu-batch-size") (void)val();   // accepted, not applicable
         else if (a == "-h" || a == "--help") { usage(); exit(0); }
         else die("unexpected argument '" + a + "'");
@@ -413,6 +426,8 @@ int parse_hex_bytes(const std::string &s, uint8_t *out, size_t cap) {
     return (int)(h.size() / 2);
 }
 
+void salt_options(const Opts &o, uint8_t salt_prefix[24], uint64_t &first);   // --salt-prefix and --salt-start, below
+
 Create2Job create2_job(const Opts &o, bool has_range, bool list) {
     if (o.cmd != "generate" || has_range) die("'-f ethereum-create2' searches salts: use it with 'generate' (no key range)");
     if (o.seed) die("the argument '--seed' cannot be used with '-f ethereum-create2' (the search walks salt counters from --salt-start)");
@@ -434,21 +449,61 @@ Create2Job create2_job(const Opts &o, bool has_range, bool list) {
         fclose(f);
         vgen_keccak256(reinterpret_cast<const uint8_t *>(code.data()), code.size(), j.init_code_hash);   // the file's bytes as they are
     }
+    salt_options(o, j.salt_prefix, j.first);
+    return j;
+}
+
+// -f ethereum-create3: the job from the command line, checked before any device is opened.
+struct Create3Job {
+    uint8_t factory[20] = {0}, proxy_hash[32] = {0}, salt_prefix[24] = {0}, guard[64] = {0};
+    int guard_len = -1;   // -1: the factory uses the raw salt
+    uint64_t first = 0;
+};
+
+// --salt-guard / --salt-guard-hash -> the guard's length (-1: none); the bytes into guard[64]
+int salt_guard(const Opts &o, uint8_t guard[64]) {
+    if (o.has_salt_guard && o.salt_guard_hash) die("the argument '--salt-guard' cannot be used with '--salt-guard-hash' ('-f ethereum-create3')");
+    if (o.salt_guard_hash) return 0;
+    if (!o.has_salt_guard) return -1;
+    const int n = parse_hex_bytes(o.salt_guard, guard, 64);
+    if (n < 0) die("--salt-guard takes 0 to 64 bytes in hex ('-f ethereum-create3')");
+    return n;
+}
+
+Create3Job create3_job(const Opts &o, bool has_range, bool list) {
+    if (o.cmd != "generate" || has_range) die("'-f ethereum-create3' searches salts: use it with 'generate' (no key range)");
+    if (o.seed) die("the argument '--seed' cannot be used with '-f ethereum-create3' (the search walks salt counters from --salt-start)");
+    if (o.random_keys) die("the argument '--random-keys' cannot be used with '-f ethereum-create3' (there are no keys)");
+    if (!o.checkpoint.empty()) die("the argument '--checkpoint' cannot be used with '-f ethereum-create3'");
+    if (list) die("the argument '--patterns-file' cannot be used with '-f ethereum-create3'");
+    if (o.has_init_code_file || o.has_init_code_hash)
+        die("the arguments '--init-code-file' and '--init-code-hash' cannot be used with '-f ethereum-create3' (the address does not depend on the init code; see --proxy-init-code-hash)");
+    Create3Job j;
+    if (!o.has_deployer) die("the following required arguments were not provided for '-f ethereum-create3': --deployer <0xFACTORY>");
+    if (parse_hex_bytes(o.deployer, j.factory, 20) != 20) die("--deployer must be an address of 20 bytes in hex");
+    if (!o.has_proxy_hash) vgen_create3_proxy_hash(j.proxy_hash);
+    else if (parse_hex_bytes(o.proxy_hash, j.proxy_hash, 32) != 32) die("--proxy-init-code-hash must be 32 bytes in hex");
+    j.guard_len = salt_guard(o, j.guard);
+    salt_options(o, j.salt_prefix, j.first);
+    return j;
+}
+
+// (the tail of the CREATE2 job's parser, kept where it stood)
+void salt_options(const Opts &o, uint8_t salt_prefix[24], uint64_t &first) {
     if (o.has_salt_prefix) {
         uint8_t pre[25];
         const std::string h = o.salt_prefix.compare(0, 2, "0x") == 0 || o.salt_prefix.compare(0, 2, "0X") == 0 ? o.salt_prefix.substr(2) : o.salt_prefix;
         if (h.size() > 48) die("--salt-prefix takes at most 24 bytes (the last 8 bytes of the salt are the counter)");
         const int n = parse_hex_bytes(o.salt_prefix, pre, 24);
         if (n < 0) die("--salt-prefix must be hex");
-        memcpy(j.salt_prefix, pre, (size_t)n);   // left-aligned, zero padded
+        memcpy(salt_prefix, pre, (size_t)n);   // left-aligned, zero padded
     }
     if (o.has_salt_start) {
         char *end = nullptr;
         errno = 0;
-        j.first = strtoull(o.salt_start.c_str(), &end, 0);
+        first = strtoull(o.salt_start.c_str(), &end, 0);
         if (errno || !end || *end || o.salt_start.empty() || o.salt_start[0] == '-') die("--salt-start must be a counter below 2^64");
     }
-    return j;
 }
 
 std::string hex0x(const uint8_t *b, size_t n) {
@@ -490,19 +545,22 @@ int run_estimate(Opts &o) {
     cfg.count = UINT64_MAX;
     cfg.case_insensitive = o.ignore_case;
     cfg.seed = fmt == VGEN_FMT_ETHEREUM_CREATE2 ? 0 : o.seed;
+    uint8_t guard[64] = {0};
+    const int guard_len = o.create3() ? salt_guard(o, guard) : -1;   // ethereum-create3: a guard costs a third block per salt
     double rate = 0;
     for (int pass = 0; pass < 2; pass++) {   // first pass warms the device up
         cfg.max_batches = pass ? 96 : 12;
         vgen_scan_result res;
         const uint8_t zero[32] = {0};   // ethereum-create2: the rate does not depend on the job
-        const int rc = fmt == VGEN_FMT_ETHEREUM_CREATE2 ? vgen_scan_create2(&c, 1, o.pattern.c_str(), zero, zero, zero, 0, &cfg, nullptr, nullptr, &g_stop, &res)
+        const int rc = o.create3() ? vgen_scan_create3(&c, 1, o.pattern.c_str(), zero, zero, zero, guard, guard_len, 0, &cfg, nullptr, nullptr, &g_stop, &res)
+                       : fmt == VGEN_FMT_ETHEREUM_CREATE2 ? vgen_scan_create2(&c, 1, o.pattern.c_str(), zero, zero, zero, 0, &cfg, nullptr, nullptr, &g_stop, &res)
                                                         : vgen_scan(c, o.pattern.c_str(), &cfg, nullptr, nullptr, &g_stop, &res);
         if (rc != VGEN_OK) die(vgen_last_error(c));
         rate = res.elapsed_secs > 0 ? (double)res.operations / res.elapsed_secs : 0.0;
         vgen_scan_result_free(&res);
     }
     vgen_destroy(c);
-    printf("Pattern: %s\nFormat: %s\nCase insensitive: %s\n\n", o.pattern.c_str(), format_display(fmt),
+    printf("Pattern: %s\nFormat: %s\nCase insensitive: %s\n\n", o.pattern.c_str(), o.create3() ? "Ethereum contract (CREATE3)" : format_display(fmt),
            o.ignore_case ? "true" : "false");
     printf("Estimated difficulty: 1 in %llu\n", (unsigned long long)difficulty);
     printf("Benchmark rate: %.0f addr/sec\n", rate);
@@ -574,10 +632,15 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
     if (o.no_gpu) die("--no-gpu: this build has no CPU scan path (the MI355X engine is the only backend)");
     const int fmt = format_id(o.format);
     const bool create2 = fmt == VGEN_FMT_ETHEREUM_CREATE2;
+    const bool create3 = o.create3();   // (then `create2` holds as well: the same context, scan loop and outputs, another job)
     if (!create2 && o.any_create2_option())
         die("'--deployer', '--init-code-hash', '--init-code-file', '--salt-prefix' and '--salt-start' belong to '-f ethereum-create2'");
+    if (!create3 && o.any_create3_option())
+        die("'--proxy-init-code-hash', '--salt-guard' and '--salt-guard-hash' belong to '-f ethereum-create3'");
     Create2Job job;
-    if (create2) job = create2_job(o, has_range, list != nullptr);
+    Create3Job job3;
+    if (create3) job3 = create3_job(o, has_range, list != nullptr);
+    else if (create2) job = create2_job(o, has_range, list != nullptr);
     // surface pattern errors before touching the device (Pattern::new, pattern.rs:21-33)
     if (!list) {
         vgen_filter *probe = nullptr;
@@ -649,7 +712,9 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
     for (uint64_t rep = 0; rep < (o.repeat ? o.repeat : 1) && !g_stop; rep++) {   // lib.rs:825-865
         vgen_scan_result res;
         prog.base = total_ops;
-        int rc = create2 ? vgen_scan_create2(ctxs.data(), (uint32_t)ctxs.size(), pattern.c_str(), job.deployer, job.init_code_hash, job.salt_prefix, job.first, &cfg,
+        int rc = create3 ? vgen_scan_create3(ctxs.data(), (uint32_t)ctxs.size(), pattern.c_str(), job3.factory, job3.proxy_hash, job3.salt_prefix, job3.guard,
+                                             job3.guard_len, job3.first, &cfg, show_progress ? progress_cb : nullptr, &prog, &g_stop, &res)
+                 : create2 ? vgen_scan_create2(ctxs.data(), (uint32_t)ctxs.size(), pattern.c_str(), job.deployer, job.init_code_hash, job.salt_prefix, job.first, &cfg,
                                              show_progress ? progress_cb : nullptr, &prog, &g_stop, &res)
                  : list ? vgen_scan_list(ctxs.data(), (uint32_t)ctxs.size(), list, o.per_pattern, &cfg, show_progress ? progress_cb : nullptr,
                                        &prog, &g_stop, &res)
@@ -679,7 +744,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
     FILE *w = stdout;
     if (!o.file.empty() && !(w = fopen(o.file.c_str(), "w"))) die("Failed to create output file");
     const double rate = total_secs > 0 ? (double)total_ops / total_secs : 0.0;
-    const std::string fmt_name = format_display(fmt);
+    const std::string fmt_name = create3 ? "Ethereum contract (CREATE3)" : format_display(fmt);
     if (o.output == "csv" && !all.empty())
         fprintf(w, "address,wif,private_key_hex,format,pattern,operations,elapsed_secs,rate%s\n", score_flt ? ",score" : "");
     for (size_t idx = 0; idx < all.size(); idx++) {
@@ -691,9 +756,25 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             die("malformed or out-of-range secret key");
         // ethereum-create2: the "key" is the salt; the address exists only for this deployer and this init code
         std::string c2_hash;
-        if (create2) {
+        if (create2 && !create3) {
             snprintf(deployer, sizeof deployer, "%s", hex0x(job.deployer, 20).c_str());
             c2_hash = hex0x(job.init_code_hash, 32);
+        }
+        // ethereum-create3: the salt is the raw one the factory is called with; the proxy and the hashed salt are recomputed here
+        std::string c3_proxy, c3_hash, c3_guarded;
+        if (create3) {
+            uint8_t proxy[20], contract[20], gs[32];
+            if (vgen_create3_address(job3.factory, g.key, job3.proxy_hash, job3.guard, job3.guard_len, proxy, contract) != VGEN_OK) die("malformed CREATE3 job");
+            snprintf(deployer, sizeof deployer, "%s", hex0x(job3.factory, 20).c_str());
+            c3_proxy = hex0x(proxy, 20);
+            c3_hash = hex0x(job3.proxy_hash, 32);
+            if (job3.guard_len >= 0) {
+                uint8_t msg[96];
+                memcpy(msg, job3.guard, (size_t)job3.guard_len);
+                memcpy(msg + job3.guard_len, g.key, 32);
+                vgen_keccak256(msg, (size_t)job3.guard_len + 32, gs);
+                c3_guarded = hex0x(gs, 32);
+            }
         }
         uint32_t score = 0;   // (score searches only: every other output stays byte for byte what it was)
         if (score_flt && vgen_score(score_flt, g.address, &score) != VGEN_OK) die("a result of a score search has no score");
@@ -702,7 +783,10 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             if (create2) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSalt    : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex);
             else fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nWIF     : %s\nHex     : %s\n", pattern.c_str(),
                          fmt_name.c_str(), g.address, g.wif, g.hex);
-            if (create2) fprintf(w, "Deployer: %s  (the factory that must run CREATE2 with the salt above)\nInitHash: %s\n", deployer, c2_hash.c_str());
+            if (create3) {
+                fprintf(w, "Deployer: %s  (the CREATE3 factory that must be called with the salt above)\nProxy   : %s\nProxyHash: %s\n", deployer, c3_proxy.c_str(), c3_hash.c_str());
+                if (!c3_guarded.empty()) fprintf(w, "GuardedSalt: %s\n", c3_guarded.c_str());
+            } else if (create2) fprintf(w, "Deployer: %s  (the factory that must run CREATE2 with the salt above)\nInitHash: %s\n", deployer, c2_hash.c_str());
             else if (deployer[0]) fprintf(w, "Deployer: %s  (the account of this key; its first transaction must create the contract)\n", deployer);
             if (score_flt) fprintf(w, "Score   : %u\n", score);
             if (!o.quiet) {
@@ -715,7 +799,10 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             const char *nl = pretty ? "\n  " : "", *sp = pretty ? " " : "";
             fprintf(w, "{%s\"address\":%s%s,", nl, sp, json_str(g.address).c_str());
             if (deployer[0]) fprintf(w, "%s\"deployer\":%s%s,", nl, sp, json_str(deployer).c_str());
-            if (create2) fprintf(w, "%s\"init_code_hash\":%s%s,", nl, sp, json_str(c2_hash).c_str());
+            if (create3) {
+                fprintf(w, "%s\"proxy\":%s%s,%s\"proxy_init_code_hash\":%s%s,", nl, sp, json_str(c3_proxy).c_str(), nl, sp, json_str(c3_hash).c_str());
+                if (!c3_guarded.empty()) fprintf(w, "%s\"guarded_salt\":%s%s,", nl, sp, json_str(c3_guarded).c_str());
+            } else if (create2) fprintf(w, "%s\"init_code_hash\":%s%s,", nl, sp, json_str(c2_hash).c_str());
             if (score_flt) fprintf(w, "%s\"score\":%s%u,", nl, sp, score);
             fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
                        "\"operations\":%s%llu,%s\"elapsed_secs\":%s%s,%s\"rate\":%s%s%s}\n",

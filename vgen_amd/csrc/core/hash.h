@@ -459,4 +459,102 @@ VG_HD void create2_place_counter(u32 m[22], u64 counter) {
     m[13] |= hi >> 24;
 }
 
+// ---- CREATE3: a CREATE2 of a fixed proxy, then a CREATE by that proxy with nonce 1 ------------------------------------------------
+// proxy = keccak256(0xff || factory || salt' || proxy_init_code_hash)[12:], contract = keccak256(0xd6 0x94 || proxy || 0x01)[12:];
+// salt' is the raw salt or keccak256(guard || salt) with a guard of 0 .. 64 bytes.  The twins of the two device blocks of
+// hashgen.py's PROGRAMS_CREATE3 and the message builders the kernels share with the host.
+
+// keccak256_create_addr with nonce 1: RLP of the list [acc, 1] is 0xd6 0x94 || acc || 0x01 (keccak_create1_block).
+VG_HD void keccak256_create1_addr(const u32 acc[5], u32 out[5]) {
+    u64 a[25];
+    const u32 m0 = 0x94d6u | (acc[0] << 16);
+    const u32 m1 = (acc[0] >> 16) | (acc[1] << 16), m2 = (acc[1] >> 16) | (acc[2] << 16);
+    const u32 m3 = (acc[2] >> 16) | (acc[3] << 16), m4 = (acc[3] >> 16) | (acc[4] << 16);
+    const u32 m5 = (acc[4] >> 16) | 0x01010000u;   // 0x01 = RLP of nonce 1 at byte 22, 0x01 = the padding at byte 23
+    a[0] = (u64)m0 | ((u64)m1 << 32);
+    a[1] = (u64)m2 | ((u64)m3 << 32);
+    a[2] = (u64)m4 | ((u64)m5 << 32);
+#pragma unroll
+    for (int i = 3; i < 25; i++) a[i] = 0;
+    a[16] = 0x8000000000000000ULL;   // last byte of the 136-byte rate block
+    keccak_f1600(a);
+    out[0] = (u32)(a[1] >> 32);
+    out[1] = (u32)a[2];
+    out[2] = (u32)(a[2] >> 32);
+    out[3] = (u32)a[3];
+    out[4] = (u32)(a[3] >> 32);
+}
+
+// The whole Keccak-256 digest (eight words in memory order) of a message of at most 103 bytes given as its 26 little-endian words
+// WITH the padding's 0x01 already in place (create3_guard_message): what keccak_guard_block takes.
+VG_HD void keccak256_guard_digest(const u32 w[26], u32 out[8]) {
+    u64 a[25];
+#pragma unroll
+    for (int i = 0; i < 13; i++) a[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
+#pragma unroll
+    for (int i = 13; i < 25; i++) a[i] = 0;
+    a[16] = 0x8000000000000000ULL;   // last byte of the 136-byte rate block
+    keccak_f1600(a);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        out[2 * i] = (u32)a[i];
+        out[2 * i + 1] = (u32)(a[i] >> 32);
+    }
+}
+
+// The 26 words of the guarded message guard[guard_len] || salt_prefix[24] || 0^8 (counter 0) with the padding's 0x01 at byte
+// guard_len + 32 (word 24 when guard_len = 64); guard_len 0 .. 64.
+VG_HD void create3_guard_message(const uint8_t *guard, int guard_len, const uint8_t salt_prefix[24], u32 w[26]) {
+    uint8_t b[104];
+    for (int i = 0; i < 104; i++) b[i] = 0;
+    for (int i = 0; i < guard_len; i++) b[i] = guard[i];
+    for (int i = 0; i < 24; i++) b[guard_len + i] = salt_prefix[i];
+    b[guard_len + 32] = 0x01;
+    for (int i = 0; i < 26; i++) w[i] = (u32)b[4 * i] | ((u32)b[4 * i + 1] << 8) | ((u32)b[4 * i + 2] << 16) | ((u32)b[4 * i + 3] << 24);
+}
+
+// The counter of a guarded candidate: bytes off .. off + 7 of the guarded message, off = guard_len + 24 (24 .. 88), big-endian.
+// `off` is uniform over a dispatch but no compile-time constant: the pass below selects on the word index and never indexes w by
+// it, so w stays in registers on the device.  w holds the message of counter 0.
+VG_HD void create3_guard_place_counter(u32 w[26], u32 off, u64 counter) {
+    const u64 v = (u64)bswap32((u32)(counter >> 32)) | ((u64)bswap32((u32)counter) << 32);   // the eight bytes as a little-endian lane
+    const u32 q = off >> 2, s = (off & 3u) * 8u;
+    const u32 x0 = (u32)(v << s), x1 = (u32)(v >> (32u - s)), x2 = (u32)((v >> 32) >> (32u - s));
+#pragma unroll
+    for (u32 k = 6; k < 25; k++) w[k] |= (k == q ? x0 : 0u) | (k == q + 1u ? x1 : 0u) | (k == q + 2u ? x2 : 0u);
+}
+
+// The digest of the guard stage as the salt of the proxy stage: its 32 bytes into message bytes 21..52 of the CREATE2 message.
+// m holds the message with an all-zero salt; the job's byte in word 5 and its three bytes in word 13 are kept.
+VG_HD void create3_place_digest(u32 m[22], const u32 d[8]) {
+    m[5] |= d[0] << 8;
+#pragma unroll
+    for (int k = 1; k < 8; k++) m[5 + k] = (d[k - 1] >> 24) | (d[k] << 8);
+    m[13] |= d[7] >> 24;
+}
+
+// CREATE3 on the host, any salt: proxy (may be nullptr) and contract as 20 bytes; guard_len < 0 = no guard.
+VG_HD void create3_address(const uint8_t factory[20], const uint8_t salt[32], const uint8_t proxy_hash[32], const uint8_t *guard, int guard_len,
+                           u32 proxy_out[5], u32 out[5]) {
+    u32 m[22], proxy[5];
+    if (guard_len < 0) {
+        create2_message(factory, salt, proxy_hash, m);
+    } else {
+        u32 w[26], d[8];
+        uint8_t zero[32];
+        for (int i = 0; i < 32; i++) zero[i] = 0;
+        create3_guard_message(guard, guard_len, salt, w);
+        u64 counter = 0;
+        for (int i = 0; i < 8; i++) counter = counter << 8 | salt[24 + i];
+        create3_guard_place_counter(w, (u32)guard_len + 24u, counter);
+        keccak256_guard_digest(w, d);
+        create2_message(factory, zero, proxy_hash, m);
+        create3_place_digest(m, d);
+    }
+    keccak256_create2_addr(m, proxy);
+    keccak256_create1_addr(proxy, out);
+    if (proxy_out)
+        for (int i = 0; i < 5; i++) proxy_out[i] = proxy[i];
+}
+
 }  // namespace vg

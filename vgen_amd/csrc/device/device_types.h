@@ -251,4 +251,30 @@ struct Create2ScoreArgs {
     unsigned long long *hits;    // one bit per slot (batch / 64 words)
 };
 
+// ---- CREATE3 jobs of a VGF_ETHEREUM_CREATE2 context (appended: no structure above changes) -------------------------------------
+// Arguments of create3_kernel: lane i tests counter first + i.  Unguarded, m is the proxy stage's message of counter 0 as in
+// Create2Args (the job's factory and proxy_init_code_hash) and w is unused.  Guarded, w is the guard stage's message of counter 0
+// with its padding (core/hash.h create3_guard_message), the counter's bytes start at byte guard_off = guard_len + 24 of it, and m
+// is the proxy stage's message with an all-zero salt, which the guard stage's digest fills.
+struct Create3Args {
+    uint32_t m[22];
+    uint32_t w[26];
+    uint32_t guard_off;
+    unsigned long long first;
+    uint32_t *payloads;          // the CONTRACT's address: slot i at payloads + 5 i, every slot (DUMP) or the slots of hit lanes only
+    unsigned long long *hits;    // !DUMP: the hit mask, one bit per slot (batch / 64 words)
+    const DevFilter *filter;     // !DUMP: the context's prefilter (kinds 1 - 3)
+};
+
+// Arguments of create3_score_kernel: Create3Args with the score terms in place of the prefilter.
+struct Create3ScoreArgs {
+    ScoreTerms terms;
+    uint32_t m[22];
+    uint32_t w[26];
+    uint32_t guard_off;
+    unsigned long long first;
+    uint32_t *out;               // payloads of hit lanes only, slot i at out + 5 i
+    unsigned long long *hits;    // one bit per slot (batch / 64 words)
+};
+
 }  // namespace vg

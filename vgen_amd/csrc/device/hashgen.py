@@ -393,6 +393,39 @@ def prog_keccak_create2(grouped=False):
     return p, "const u32 w[22]", prologue
 
 
+def prog_keccak_create1(grouped=False):
+    """CREATE3, last stage: the address of the contract the proxy deploys with nonce 1, the low 20 bytes of
+    Keccak-256(0xd6 0x94 || A || 0x01) (core/hash.h keccak256_create1_addr).  prog_keccak_create's program with the nonce byte 0x01 in
+    place of 0x80: message byte 22 = 0x01, the padding's 0x01 at byte 23."""
+    p = Program(grouped)
+    lanes = [(p.input(f"m{2 * i}"), p.input(f"m{2 * i + 1}")) for i in range(3)] + [(0, 0)] * 22
+    lanes[16] = (0, 0x80000000)
+    a = p.keccak_f1600(lanes)
+    p.outputs = [a[1][1], a[2][0], a[2][1], a[3][0], a[3][1]]
+    p.prune()
+    prologue = ["u32 m0 = 0x94d6u | (a[0] << 16);"]
+    # m_i = (a[i - 1] >> 16) | (a[i] << 16) as the funnel shift the block itself rotates with: left to hipcc the expression becomes
+    # v_perm_b32, an instruction of the same issue class, and the kernels' ISA contract counts funnel shifts by v_alignbit_b32
+    prologue += ["u32 m1, m2, m3, m4;"]
+    prologue += [f'asm("v_alignbit_b32 %0, %1, %2, 16" : "=v"(m{i}) : "v"(a[{i}]), "v"(a[{i - 1}]));' for i in range(1, 5)]
+    prologue += ["u32 m5 = (a[4] >> 16) | 0x01010000u;"]
+    return p, "const u32 a[5]", prologue
+
+
+def prog_keccak_guard(grouped=False):
+    """CREATE3, guarded salts: the whole digest of keccak256(guard || salt), a message of at most 96 bytes, so one rate block
+    (core/hash.h keccak256_guard_digest).  w = 26 words, lanes 0..12, prepared by the host INCLUDING the 0x01 of the padding at byte
+    guard_len + 32 (it may land in word 24); lane 16 ends the block.  Pruned to the eight words of the digest."""
+    p = Program(grouped)
+    lanes = [(p.input(f"m{2 * i}"), p.input(f"m{2 * i + 1}")) for i in range(13)] + [(0, 0)] * 12
+    lanes[16] = (0, 0x80000000)
+    a = p.keccak_f1600(lanes)
+    p.outputs = [a[i][h] for i in range(4) for h in range(2)]
+    p.prune()
+    prologue = [f"u32 m{i} = w[{i}];" for i in range(26)]
+    return p, "const u32 w[26]", prologue
+
+
 # keccak_addr_block: in round 4, in dependency order, the block ran no faster than hipcc's rolled rounds (same 5 003 instructions per key); as runs by
 # issue class with the priority changes it is worth +28 % on every Ethereum configuration (profiles/r05_keccak_ab.txt): 1 351 half-rate funnel
 # shifts against 2 844 full-rate booleans, which now ride in the second places of the issue slots.
@@ -404,7 +437,10 @@ PROGRAMS_CONTRACT = {"keccak_create_block": prog_keccak_create}
 # yields per function where they differ from the default
 # the one block of VGF_ETHEREUM_CREATE2 (create2_kernel); again a table of its own, emitted after the two above
 PROGRAMS_CREATE2 = {"keccak_create2_block": prog_keccak_create2}
-YIELDS = {"keccak_addr_block": "none", "keccak_create_block": "none", "keccak_create2_block": "none"}
+# the two further blocks of a CREATE3 job on a VGF_ETHEREUM_CREATE2 context (create3_kernel); a third table, emitted last
+PROGRAMS_CREATE3 = {"keccak_create1_block": prog_keccak_create1, "keccak_guard_block": prog_keccak_guard}
+YIELDS = {"keccak_addr_block": "none", "keccak_create_block": "none", "keccak_create2_block": "none",
+          "keccak_create1_block": "none", "keccak_guard_block": "none"}
 
 
 # ---- the Python model of the instruction list (CPU tests) ---------------------------------------------------------------------
@@ -678,7 +714,7 @@ def add_filler(lines, mode, n):
 
 
 def function_source(name, grouped=False, yields="every:3", window=0, distance=1, prio=None, class_window=0):
-    p, params, prologue = {**PROGRAMS, **OPTIONAL, **PROGRAMS_CONTRACT, **PROGRAMS_CREATE2}[name](grouped)
+    p, params, prologue = {**PROGRAMS, **OPTIONAL, **PROGRAMS_CONTRACT, **PROGRAMS_CREATE2, **PROGRAMS_CREATE3}[name](grouped)
     left = spread(p, window, distance) if window else None
     runs = by_class(p, class_window, CLASS_DISTANCE) if class_window else None
     reg, nreg = allocate(p)
@@ -746,6 +782,15 @@ def generate_create2(grouped=False, yields=DEFAULT_YIELD, window=0, distance=1, 
     return src
 
 
+def generate_create3(grouped=False, yields=DEFAULT_YIELD, window=0, distance=1, overrides=None,
+                     prio=tuple(int(x) for x in DEFAULT_PRIO.split(":")), class_window=DEFAULT_CLASS_WINDOW):
+    """The table PROGRAMS_CREATE3 under the same options: main() writes it last, behind generate()'s and generate_create2()'s text."""
+    src = ""
+    for name in PROGRAMS_CREATE3:
+        src += function_source(name, grouped, (overrides or {}).get(name, YIELDS.get(name, yields)), window, distance, prio, class_window)
+    return src
+
+
 def main(argv):
     def opt(name, default):
         return argv[argv.index(name) + 1] if name in argv else default
@@ -767,6 +812,7 @@ def main(argv):
     class_window = int(opt("--class-window", str(DEFAULT_CLASS_WINDOW)))
     sys.stdout.write(generate(grouped, yields, window, distance, overrides, [a for i, a in enumerate(argv) if i and argv[i - 1] == "--with"], prio, class_window))
     sys.stdout.write(generate_create2(grouped, yields, window, distance, overrides, prio, class_window))
+    sys.stdout.write(generate_create3(grouped, yields, window, distance, overrides, prio, class_window))
 
 
 if __name__ == "__main__":

@@ -2171,3 +2171,117 @@ hipError_t launch_create2_score(const Create2ScoreArgs &a, uint32_t batch, const
 }
 
 }  // namespace vg
+
+// ---- CREATE3 jobs of a VGF_ETHEREUM_CREATE2 context -------------------------------------------------------------------------------
+// contract = keccak256(0xd6 0x94 || proxy || 0x01)[12:] with proxy = the CREATE2 address of a fixed proxy under the salt salt', and
+// salt' the raw salt salt_prefix || u64be(counter) or, GUARD, keccak256(guard || salt).  Two or three Keccak blocks per salt, run
+// one after another: each block's inputs are the job's uniform words and at most eight words of the block before, so the register
+// peak is one block's.  The proxy stage is keccak_create2_block as create2_kernel runs it; the payload is the contract's address
+// (the proxy's is never stored).  Dump, prefilter, ballot store and the hit lanes' payloads as in create2_kernel; kernels of their
+// own, so that the CREATE2 symbols stay what they are.
+namespace vg {
+
+template <bool GUARD>
+__device__ __forceinline__ void create3_chain(const u32 (&jm)[22], const u32 (&jw)[26], u32 guard_off, unsigned long long counter, u32 pl[5]) {
+    u32 m[22], proxy[5];
+#pragma unroll
+    for (int k = 0; k < 22; k++) m[k] = jm[k];
+    if (GUARD) {
+        u32 w[26], d[8];
+#pragma unroll
+        for (int k = 0; k < 26; k++) w[k] = jw[k];
+        create3_guard_place_counter(w, guard_off, counter);   // (selects on the uniform word index: no indexed register array)
+#if VG_KECCAK_BLOCK
+        keccak_guard_block(w, d);
+#else
+        keccak256_guard_digest(w, d);
+#endif
+        create3_place_digest(m, d);
+    } else {
+        create2_place_counter(m, counter);
+    }
+#if VG_KECCAK_BLOCK
+    keccak_create2_block(m, proxy);
+    keccak_create1_block(proxy, pl);
+#else
+    keccak256_create2_addr(m, proxy);
+    keccak256_create1_addr(proxy, pl);
+#endif
+}
+
+template <bool DUMP, bool GUARD>
+__global__ void __launch_bounds__(256) create3_kernel(const Create3Args a) {
+#if VG_BASE_PRIO && VG_KECCAK_BLOCK
+    __builtin_amdgcn_s_setprio(VG_BASE_PRIO);   // (the level the hash blocks return to)
+#endif
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    u32 pl[5];
+    create3_chain<GUARD>(a.m, a.w, a.guard_off, a.first + i, pl);
+    u32 *o = a.payloads + (size_t)i * 5;
+    if (DUMP) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) o[k] = pl[k];
+    } else {
+        const bool hit = filter_eval_n<5>(a.filter, pl);
+        const unsigned long long mask = __ballot(hit);
+        if ((threadIdx.x & 63u) == 0) a.hits[i >> 6] = mask;
+        if (hit) {
+#pragma unroll
+            for (int k = 0; k < 5; k++) o[k] = pl[k];
+        }
+    }
+}
+
+template <bool GUARD>
+__global__ void __launch_bounds__(256) create3_score_kernel(const Create3ScoreArgs a) {
+#if VG_BASE_PRIO && VG_KECCAK_BLOCK
+    __builtin_amdgcn_s_setprio(VG_BASE_PRIO);   // (the level the hash blocks return to)
+#endif
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    u32 pl[5];
+    create3_chain<GUARD>(a.m, a.w, a.guard_off, a.first + i, pl);
+    const bool hit = score_eval(a.terms, pl, nullptr);
+    const unsigned long long mask = __ballot(hit);
+    if ((threadIdx.x & 63u) == 0) a.hits[i >> 6] = mask;
+    if (hit) {
+        u32 *o = a.out + (size_t)i * 5;
+#pragma unroll
+        for (int k = 0; k < 5; k++) o[k] = pl[k];
+    }
+}
+
+static bool create3_geometry_ok(uint32_t batch, bool guarded, uint32_t guard_off) {
+    return batch != 0 && batch % 256 == 0 && (!guarded || (guard_off >= 24 && guard_off <= 88));
+}
+
+hipError_t launch_create3(const Create3Args &a, bool guarded, uint32_t batch, const PtabArgs *compact, hipStream_t stream) {
+    if (!create3_geometry_ok(batch, guarded, a.guard_off) || !a.payloads) return hipErrorInvalidValue;
+    const dim3 grid(batch / 256), wg(256);
+    if (!compact) {
+        if (guarded) hipLaunchKernelGGL((create3_kernel<true, true>), grid, wg, 0, stream, a);
+        else hipLaunchKernelGGL((create3_kernel<true, false>), grid, wg, 0, stream, a);
+        return hipGetLastError();
+    }
+    if (!a.hits || !a.filter || compact->payloads != a.payloads || compact->hits != a.hits || compact->stride != batch || compact->images != 1)
+        return hipErrorInvalidValue;
+    if (guarded) hipLaunchKernelGGL((create3_kernel<false, true>), grid, wg, 0, stream, a);
+    else hipLaunchKernelGGL((create3_kernel<false, false>), grid, wg, 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ptab_compact_kernel<5>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, *compact);
+    return hipGetLastError();
+}
+
+hipError_t launch_create3_score(const Create3ScoreArgs &a, bool guarded, uint32_t batch, const PtabArgs &compact, hipStream_t stream) {
+    if (!create3_geometry_ok(batch, guarded, a.guard_off) || !a.out || !a.hits || !score_terms_ok(a.terms)) return hipErrorInvalidValue;
+    if (compact.payloads != a.out || compact.hits != a.hits || compact.stride != batch || compact.images != 1 || !compact.mhdr || !compact.mrec)
+        return hipErrorInvalidValue;
+    if (guarded) hipLaunchKernelGGL((create3_score_kernel<true>), dim3(batch / 256), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((create3_score_kernel<false>), dim3(batch / 256), dim3(256), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ptab_compact_kernel<5>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, compact);
+    return hipGetLastError();
+}
+
+}  // namespace vg

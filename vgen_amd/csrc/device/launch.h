@@ -59,4 +59,9 @@ hipError_t launch_create2(const Create2Args &a, uint32_t batch, const PtabArgs *
 // name the same payload buffer, hit mask and geometry; a refused call launches nothing.
 hipError_t launch_payload_score(const ScoreArgs &a, const PtabArgs &compact, hipStream_t stream);
 hipError_t launch_create2_score(const Create2ScoreArgs &a, uint32_t batch, const PtabArgs &compact, hipStream_t stream);
+// A CREATE3 job on a VGF_ETHEREUM_CREATE2 context: launch_create2 / launch_create2_score with two Keccak blocks per salt (proxy, then
+// the proxy's first contract) or, `guarded`, three (the hashed salt before them).  Same rules for `compact`; a.guard_off must be
+// 24 .. 88 when guarded.
+hipError_t launch_create3(const Create3Args &a, bool guarded, uint32_t batch, const PtabArgs *compact, hipStream_t stream);
+hipError_t launch_create3_score(const Create3ScoreArgs &a, bool guarded, uint32_t batch, const PtabArgs &compact, hipStream_t stream);
 }  // namespace vg

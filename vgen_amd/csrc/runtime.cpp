@@ -230,6 +230,8 @@ int rt_device_name(int device, std::string &name, std::string &err) {
 // the device side of a CREATE2 context (defined beside the other dispatches): rt_create hands them to the context
 static int create2_set(vgen_ctx *c, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]);
 static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter);
+static int create3_set(vgen_ctx *c, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
+                       const uint8_t *guard, int guard_len);
 
 int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
     // ABI 4's parameter block, or ABI 3's 28 bytes (no table_bits, no budget: both automatic)
@@ -346,6 +348,7 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
         lap("filter + match rings");
         c->create2_set = create2_set;
         c->create2_dispatch = create2_dispatch;
+        c->create3_set = create3_set;
         *out = c;
         return VGEN_OK;
     }
@@ -1446,13 +1449,32 @@ static int create2_set(vgen_ctx *c, const uint8_t deployer[20], const uint8_t in
     memcpy(salt, salt_prefix, 24);   // counter 0: the kernel ORs the counter's bytes into words 11 - 13
     create2_message(deployer, salt, init_code_hash, c->create2_m);
     c->have_create2 = true;
+    c->have_create3 = false;   // (a CREATE2 job replaces a CREATE3 job)
+    return VGEN_OK;
+}
+
+// The CREATE3 job: the proxy stage's message as for CREATE2 - with the salt prefix when the raw salt goes in, with an all-zero
+// salt when the guard stage's digest does - and the guard stage's message of counter 0.
+static int create3_set(vgen_ctx *c, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
+                       const uint8_t *guard, int guard_len) {
+    if (guard_len < -1 || guard_len > 64 || (guard_len > 0 && !guard)) return c->fail(VGEN_E_INVALID, "vgen_set_create3: guard_len is -1 (no guard) or 0 .. 64 bytes");
+    for (auto &fr : c->fr)
+        if (fr.in_flight) return c->fail(VGEN_E_STATE, "vgen_set_create3 while a dispatch is in flight");
+    uint8_t salt[32] = {0};
+    if (guard_len < 0) memcpy(salt, salt_prefix, 24);
+    create2_message(factory, salt, proxy_init_code_hash, c->create2_m);
+    memset(c->create3_w, 0, sizeof c->create3_w);
+    if (guard_len >= 0) create3_guard_message(guard, guard_len, salt_prefix, c->create3_w);
+    c->create3_guard_len = guard_len;
+    c->have_create3 = true;
+    c->have_create2 = false;
     return VGEN_OK;
 }
 
 // One kernel per dispatch (plus the list path's kernels behind it where the filter needs them), on the frame's own stream.
 static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter) {
     if (frame >= c->frames) return c->fail(VGEN_E_INVALID, "bad frame index");
-    if (!c->have_create2) return c->fail(VGEN_E_STATE, "vgen_dispatch_create2 before vgen_set_create2");
+    if (!c->have_create2 && !c->have_create3) return c->fail(VGEN_E_STATE, "vgen_dispatch_create2 before vgen_set_create2");
     if (first_counter > UINT64_MAX - (c->batch - 1)) return c->fail(VGEN_E_RANGE, "vgen_dispatch_create2: the counter range passes 2^64 - 1");
     vgen_ctx::Frame &f = c->fr[frame];
     if (f.in_flight) return c->fail(VGEN_E_STATE, "frame already has a dispatch in flight");
@@ -1493,8 +1515,33 @@ static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter)
         HIP_TRY(c, hipEventRecord(f.ev_start, f.s));
         HIP_TRY(c, hipEventRecord(f.ev_mid, f.s));
     }
-    if (scored) {   // hash, score and the hit lanes' payloads in one kernel, then the compaction
-        if (c->score.n == 0) return c->fail(VGEN_E_STATE, "the context's score filter has no terms (vgen_set_filter installs them)");
+    if (scored && c->score.n == 0) return c->fail(VGEN_E_STATE, "the context's score filter has no terms (vgen_set_filter installs them)");
+    if (c->have_create3) {   // the same dispatch with the chained kernels: two blocks per salt, three with a guard
+        const bool guarded = c->create3_guard_len >= 0;
+        if (scored) {
+            Create3ScoreArgs sa;
+            memset(&sa, 0, sizeof sa);
+            sa.terms = c->score;
+            memcpy(sa.m, a.m, sizeof sa.m);
+            memcpy(sa.w, c->create3_w, sizeof sa.w);
+            sa.guard_off = guarded ? (uint32_t)c->create3_guard_len + 24u : 0u;
+            sa.first = a.first;
+            sa.hits = f.d_hits;
+            sa.out = f.d_list;
+            HIP_TRY(c, launch_create3_score(sa, guarded, c->batch, p, f.s));
+        } else {
+            Create3Args a3;
+            memset(&a3, 0, sizeof a3);
+            memcpy(a3.m, a.m, sizeof a3.m);
+            memcpy(a3.w, c->create3_w, sizeof a3.w);
+            a3.guard_off = guarded ? (uint32_t)c->create3_guard_len + 24u : 0u;
+            a3.first = a.first;
+            a3.payloads = a.payloads;
+            a3.hits = a.hits;
+            a3.filter = a.filter;
+            HIP_TRY(c, launch_create3(a3, guarded, c->batch, inl ? &p : nullptr, f.s));
+        }
+    } else if (scored) {   // hash, score and the hit lanes' payloads in one kernel, then the compaction
         Create2ScoreArgs sa;
         memset(&sa, 0, sizeof sa);
         sa.terms = c->score;

@@ -84,6 +84,15 @@ struct vgen_ctx {
     // scanner.cpp reach the CREATE2 job and dispatch through these, so the rt_* interface below stays what the stand-in implements
     int (*create2_set)(vgen_ctx *, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]) = nullptr;
     int (*create2_dispatch)(vgen_ctx *, uint32_t frame, uint64_t first_counter) = nullptr;
+    // A CREATE3 job on such a context (vgen_set_create3; it and a CREATE2 job replace each other, create2_dispatch runs whichever is
+    // installed): create2_m is then the proxy stage's message (the factory, proxy_init_code_hash and - unguarded - the salt prefix),
+    // create3_guard_len the guard's length (-1: no guard) and create3_w the guard stage's message of counter 0 with its padding
+    // (core/hash.h create3_guard_message).  create3_set is set by a runtime that knows CREATE3 jobs, nullptr elsewhere.
+    bool have_create3 = false;
+    int create3_guard_len = -1;
+    uint32_t create3_w[26] = {0};
+    int (*create3_set)(vgen_ctx *, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
+                       const uint8_t *guard, int guard_len) = nullptr;
     // DEVF_SCORE: the terms of the installed score filter (set by rt_set_filter, the first threshold replaced by vgen_set_score_min;
     // n = 0 for every other filter and in dump mode).  Copied by value into each dispatch's kernel arguments.
     vg::ScoreTerms score{};
@@ -214,6 +223,11 @@ void rt_prefer_table_bits(vgen_ctx *ctx, uint32_t bits, uint32_t cap = 0);
 inline int rt_set_create2(vgen_ctx *ctx, const uint8_t deployer[20], const uint8_t init_code_hash[32], const uint8_t salt_prefix[24]) {
     if (!ctx->create2_set) return ctx->fail(VGEN_E_INVALID, "vgen_set_create2: the context was not created for the ethereum-create2 format (7)");
     return ctx->create2_set(ctx, deployer, init_code_hash, salt_prefix);
+}
+inline int rt_set_create3(vgen_ctx *ctx, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
+                          const uint8_t *guard, int guard_len) {
+    if (!ctx->create3_set) return ctx->fail(VGEN_E_INVALID, "vgen_set_create3: the context was not created for the ethereum-create2 format (7)");
+    return ctx->create3_set(ctx, factory, proxy_init_code_hash, salt_prefix, guard, guard_len);
 }
 inline int rt_dispatch_create2(vgen_ctx *ctx, uint32_t frame, uint64_t first_counter) {
     if (!ctx->create2_dispatch) return ctx->fail(VGEN_E_INVALID, "vgen_dispatch_create2: the context was not created for the ethereum-create2 format (7)");

@@ -17,6 +17,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <mutex>
 #include <memory>
 #include <random>
@@ -1023,22 +1024,25 @@ void create2_drain(Create2Lane &l) {
 
 }  // namespace
 
-extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const uint8_t deployer[20], const uint8_t init_code_hash[32],
-                                 const uint8_t salt_prefix[24], uint64_t first_counter, const vgen_scan_config *cfg_in, vgen_progress_cb cb,
-                                 void *user, const volatile int32_t *stop, vgen_scan_result *out) {
+// The salt scan of both kinds of job: `what` names the entry point in messages, `install` puts the job on a context, `salt_prefix`
+// is the caller's part of the raw salt, which is what a result's key holds.
+static int salt_scan_run(const char *what, const std::function<int(vgen_ctx *)> &install, vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern,
+                         const uint8_t salt_prefix[24], uint64_t first_counter, const vgen_scan_config *cfg_in, vgen_progress_cb cb,
+                         void *user, const volatile int32_t *stop, vgen_scan_result *out) {
     vgen_scan_config c;
-    if (!pattern || !deployer || !init_code_hash || !salt_prefix || !multi_args(ctxs, n_ctx, cfg_in, c, out)) return VGEN_E_INVALID;
+    if (!pattern || !salt_prefix || !multi_args(ctxs, n_ctx, cfg_in, c, out)) return VGEN_E_INVALID;
     vgen_ctx *c0 = ctxs[0];
-    if (c.format != VGF_ETHEREUM_CREATE2) return c0->fail(VGEN_E_INVALID, "vgen_scan_create2: the scan format must be ethereum-create2 (7)");
+    const std::string name = what;
+    if (c.format != VGF_ETHEREUM_CREATE2) return c0->fail(VGEN_E_INVALID, name + ": the scan format must be ethereum-create2 (7)");
     for (uint32_t i = 0; i < n_ctx; i++) {
-        if (ctxs[i]->format != VGF_ETHEREUM_CREATE2) return c0->fail(VGEN_E_INVALID, "vgen_scan_create2: a context was not created for the ethereum-create2 format (7)");
+        if (ctxs[i]->format != VGF_ETHEREUM_CREATE2) return c0->fail(VGEN_E_INVALID, name + ": a context was not created for the ethereum-create2 format (7)");
         for (auto &f : ctxs[i]->fr)
-            if (f.in_flight) return c0->fail(VGEN_E_STATE, "vgen_scan_create2 while a dispatch is in flight");
+            if (f.in_flight) return c0->fail(VGEN_E_STATE, name + " while a dispatch is in flight");
     }
     if ((c.flags & VGEN_SCAN_BEST) && c.checkpoint_path)
         return c0->fail(VGEN_E_UNSUPPORTED, "the scan flag `best` (vgen_scan_config.flags = 2) together with checkpoint_path is not supported: a resumed scan would not know the scores reported before");
     if (c.has_start || c.has_end || c.seed || c.shard || c.n_shards > 1 || c.checkpoint_path || (c.flags & ~VGEN_SCAN_BEST))
-        return c0->fail(VGEN_E_UNSUPPORTED, "vgen_scan_create2 reads format, count, case_insensitive, max_batches and the scan flag `best` (2): start / end, seed, shards, checkpoints and other flags do not apply to a salt search");
+        return c0->fail(VGEN_E_UNSUPPORTED, name + " reads format, count, case_insensitive, max_batches and the scan flag `best` (2): start / end, seed, shards, checkpoints and other flags do not apply to a salt search");
     const auto t0 = std::chrono::steady_clock::now();
     vgen_filter flt;
     std::string err;
@@ -1056,7 +1060,7 @@ extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pa
         l.ctx = ctxs[i];
         l.next = i;
         l.nframes = l.ctx->frames;
-        if ((rc = rt_set_create2(l.ctx, deployer, init_code_hash, salt_prefix)) != VGEN_OK) break;
+        if ((rc = install(l.ctx)) != VGEN_OK) break;
         if ((rc = vgen_set_filter(l.ctx, &flt)) != VGEN_OK) break;   // (through the C entry point: it also installs a score filter's terms)
         if (dump) {
             uint32_t df = 0;
@@ -1065,7 +1069,7 @@ extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pa
         }
     }
     if (rc != VGEN_OK) {
-        if (c0->err.empty()) c0->err = "vgen_scan_create2: a context refused the job or the filter (vgen_last_error of that context)";
+        if (c0->err.empty()) c0->err = name + ": a context refused the job or the filter (vgen_last_error of that context)";
         return rc;
     }
     auto stopped = [&]() { return stop && __atomic_load_n(const_cast<const int32_t *>(stop), __ATOMIC_RELAXED) != 0; };
@@ -1134,7 +1138,7 @@ extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pa
             const std::string addr = address_from_payload(c.format, payload);
             LiteMatch m;
             if (addr.empty() || addr.size() >= sizeof m.address || !filter_accepts(flt, addr, payload)) continue;
-            memcpy(m.key, salt_prefix, 24);   // the "key" of a CREATE2 result is the salt
+            memcpy(m.key, salt_prefix, 24);   // the "key" of a result is the (raw) salt
             const uint64_t counter = base + index;
             for (int b = 0; b < 8; b++) m.key[24 + b] = (uint8_t)(counter >> (8 * (7 - b)));
             memcpy(m.address, addr.c_str(), addr.size() + 1);
@@ -1180,6 +1184,24 @@ extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pa
     }
     out->complete = complete ? 1 : 0;
     return VGEN_OK;
+}
+
+extern "C" int vgen_scan_create2(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const uint8_t deployer[20], const uint8_t init_code_hash[32],
+                                 const uint8_t salt_prefix[24], uint64_t first_counter, const vgen_scan_config *cfg_in, vgen_progress_cb cb,
+                                 void *user, const volatile int32_t *stop, vgen_scan_result *out) {
+    if (!deployer || !init_code_hash || !salt_prefix) return VGEN_E_INVALID;
+    return salt_scan_run("vgen_scan_create2", [&](vgen_ctx *ctx) { return rt_set_create2(ctx, deployer, init_code_hash, salt_prefix); }, ctxs, n_ctx,
+                         pattern, salt_prefix, first_counter, cfg_in, cb, user, stop, out);
+}
+
+// The same loop over a CREATE3 job: the device reports the contract's address, a result's key is the raw salt the caller passes
+// to the factory (the guarded salt and the proxy are recomputed by whoever prints them: vgen_create3_address).
+extern "C" int vgen_scan_create3(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32],
+                                 const uint8_t salt_prefix[24], const uint8_t *guard, int32_t guard_len, uint64_t first_counter,
+                                 const vgen_scan_config *cfg_in, vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out) {
+    if (!factory || !proxy_init_code_hash || !salt_prefix || guard_len < -1 || guard_len > 64 || (guard_len > 0 && !guard)) return VGEN_E_INVALID;
+    return salt_scan_run("vgen_scan_create3", [&](vgen_ctx *ctx) { return rt_set_create3(ctx, factory, proxy_init_code_hash, salt_prefix, guard, guard_len); },
+                         ctxs, n_ctx, pattern, salt_prefix, first_counter, cfg_in, cb, user, stop, out);
 }
 
 extern "C" void vgen_scan_result_free(vgen_scan_result *r) {
