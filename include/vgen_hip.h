@@ -63,6 +63,18 @@ typedef enum vgen_format {
                                         dispatches and scans refuse the format; vgen_set_create2 / vgen_dispatch_create2 / vgen_scan_create2
                                         drive it.  Payload, address string, filters and difficulty as for VGEN_FMT_ETHEREUM. */
 } vgen_format;
+/* One more format, outside the enumeration: VGEN_FMT_NOSTR, 10 (not a format of the reference).  The numbers 8 and 9 stay
+ * unassigned: every entry point answers them as unknown formats.  The Nostr public key (NIP-19 "npub1..."), i.e. the BIP-340
+ * x-only key itself.  Payload: the 32 bytes of x(k*G), big-endian, no hash and no tweak.  Address string: Bech32 (BIP-173,
+ * constant 1 - not Bech32m) with HRP "npub" and no witness-version symbol: 52 data symbols (the last carries one key bit and four
+ * zero pad bits: 'q' or 's') + 6 checksum symbols, 63 characters.  In vgen_generated, `wif` holds "nsec1..." (Bech32, HRP "nsec",
+ * of the scalar as found - no parity normalisation, BIP-340 signers negate internally) and `hex` the scalar.  On a VGEN_FLAG_ENDO
+ * context a point has THREE images, not six ((x, y) and (x, -y) are one x-only key): keys_tested = 3 x batch_size, image e of key
+ * i at e * batch_size + i, vgen_key_variant 0..2.  Prefix / suffix masks run inside the per-key kernel (hit mask +
+ * compaction, no atomic); on-device automata and pattern lists over the frame's device-only payload buffer (32 B per key, x 3 with
+ * VGEN_FLAG_ENDO).
+ * No score patterns. */
+#define VGEN_FMT_NOSTR 10u
 
 /* Parameters of vgen_create; replaces the arguments of GpuRunner::new(batch_size, backend)
  * (src/gpu.rs:138) plus the buffer sizing it derives from them (src/gpu.rs:391-500). */
@@ -75,7 +87,8 @@ typedef enum vgen_format {
                                  vgen_scan refuses start / end / seed on such a context.  vgen_wait reports keys_tested
                                  = 6 x batch_size and match indices variant * batch_size + i (vgen_key_variant).  The
                                  arbitrary-scalar dispatches (vgen_dispatch_keys, vgen_dispatch_random) test the six images of
-                                 every scalar's point in the same way (keys_tested = 6 x n, same index convention). */
+                                 every scalar's point in the same way (keys_tested = 6 x n, same index convention).
+                                 VGEN_FMT_NOSTR: three images, not six (see there): read 3 for 6 throughout. */
 #define VGEN_FLAG_TIMING 1u   /* record HIP events around every dispatch so that vgen_frame_kernel_ms /
                                  vgen_frame_dispatch_ms report durations (bench.py); without it a dispatch is
                                  three kernels and one copy, and the host loop is ~10 us per step cheaper */
@@ -377,6 +390,11 @@ int vgen_key_add(const uint8_t key_be[32], uint64_t amount, uint8_t out_be[32]);
  * This maps the base key start_key + i to the key of `variant`: 0..2 = lambda^variant * k, 3..5 = the negations
  * (mod n; lambda * (x, y) = (beta * x, y) on secp256k1).  VGEN_E_RANGE for an invalid key. */
 int vgen_key_variant(const uint8_t key_be[32], uint32_t variant, uint8_t out_be[32]);
+/* NIP-19 bare keys (VGEN_FMT_NOSTR): Bech32 of 32 bytes under HRP "npub" (kind 0: an x-only public key) or "nsec" (kind 1: a secret
+ * key).  vgen_nostr_encode returns the length (63) or a negative status.  vgen_nostr_decode is strict: VGEN_E_INVALID for another
+ * HRP, another length, mixed case, non-zero pad bits, a symbol outside the alphabet or a bad checksum; *kind receives 0 or 1. */
+int vgen_nostr_encode(uint32_t kind, const uint8_t data[32], char *out, size_t cap);
+int vgen_nostr_decode(const char *text, uint32_t *kind, uint8_t out[32]);
 /* AddressGenerator::generate (src/address.rs:92-151) on the host, for single keys (verify-style
  * use and tests). address cap >= 96, wif cap >= 72. VGEN_E_RANGE for an invalid key. */
 int vgen_derive(uint32_t format, const uint8_t key_be[32], char *address, size_t acap, char *wif, size_t wcap);

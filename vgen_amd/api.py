@@ -56,6 +56,17 @@ class AddressFormat(enum.IntEnum):
         return _L.vgen_format_charset_name(int(self)).decode()
 
 
+# VGEN_FMT_NOSTR: the Nostr public key npub1... (NIP-19), the BIP-340 x-only key itself (not in the reference).  A plain number outside
+# the enumeration, as in the header (8 and 9 stay unassigned); every function that takes a format takes it.
+FORMAT_NOSTR = 10
+
+
+def _fmt(v):
+    """A format as callers see it: the AddressFormat member, or the plain number of a format outside the enumeration."""
+    v = int(v)
+    return AddressFormat(v) if v in AddressFormat._value2member_map_ else v
+
+
 class _Params(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("device", ctypes.c_int32), ("batch_size", ctypes.c_uint32),
                 ("format", ctypes.c_uint32), ("frames", ctypes.c_uint32), ("match_cap", ctypes.c_uint32),
@@ -148,6 +159,8 @@ _L.vgen_derive.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ct
                            ctypes.c_size_t]
 _L.vgen_contract_address.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
 _L.vgen_keccak256.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
+_L.vgen_nostr_encode.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+_L.vgen_nostr_decode.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p]
 _L.vgen_create2_address.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
 _L.vgen_create2_salt.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
 _L.vgen_set_create2.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
@@ -248,6 +261,31 @@ def key_variant(key, variant):
     out = ctypes.create_string_buffer(32)
     _check(_L.vgen_key_variant(_key(key), variant, out))
     return int.from_bytes(out.raw, "big")
+
+
+def nostr_encode(kind: str, data: bytes) -> str:
+    """vgen_nostr_encode: NIP-19 Bech32 of 32 bytes; kind "npub" (an x-only public key) or "nsec" (a secret key)."""
+    out = ctypes.create_string_buffer(128)
+    _check(_L.vgen_nostr_encode({"npub": 0, "nsec": 1}[kind], bytes(data), out, 128))
+    return out.value.decode()
+
+
+def nostr_decode(text: str):
+    """vgen_nostr_decode (strict) -> (kind, 32 bytes), or None when `text` is no npub / nsec string."""
+    kind, out = ctypes.c_uint32(), ctypes.create_string_buffer(32)
+    if _L.vgen_nostr_decode(text.encode(), ctypes.byref(kind), out) != 0:
+        return None
+    return ("npub", "nsec")[kind.value], out.raw
+
+
+def npub_from_key(key) -> str:
+    """The Nostr public key npub1... of a secret key (an integer or 32 big-endian bytes): Bech32 of x(key * G)."""
+    return derive(FORMAT_NOSTR, key).address
+
+
+def nsec_from_key(key) -> str:
+    """The NIP-19 rendering nsec1... of a secret key, as it is (no parity normalisation)."""
+    return key_to_wif(FORMAT_NOSTR, key)
 
 
 def contract_address(deployer, nonce=0) -> bytes:
@@ -389,14 +427,14 @@ def derive(fmt, key) -> Optional[GeneratedAddress]:
     if rc == E_RANGE:
         return None
     _check(rc)
-    return GeneratedAddress(a.value.decode(), w.value.decode(), _key(key).hex(), AddressFormat(int(fmt)))
+    return GeneratedAddress(a.value.decode(), w.value.decode(), _key(key).hex(), _fmt(fmt))
 
 
 class Pattern:
     """Pattern::new / matches (src/pattern.rs:21-45) plus the device prefilter derived for `fmt`."""
 
     def __init__(self, pattern: str, case_insensitive: bool = False, fmt: AddressFormat = AddressFormat.P2pkh):
-        self.original, self.case_insensitive, self.format = pattern, case_insensitive, AddressFormat(int(fmt))
+        self.original, self.case_insensitive, self.format = pattern, case_insensitive, _fmt(fmt)
         h = ctypes.c_void_p()
         _check(_L.vgen_filter_compile(pattern.encode(), int(case_insensitive), int(fmt), ctypes.byref(h)))
         self._h = h
@@ -459,7 +497,7 @@ class PatternList:
 
     def __init__(self, patterns, case_insensitive: bool = False, fmt: AddressFormat = AddressFormat.P2pkh):
         text = patterns if isinstance(patterns, str) else "\n".join(patterns)
-        self.case_insensitive, self.format = case_insensitive, AddressFormat(int(fmt))
+        self.case_insensitive, self.format = case_insensitive, _fmt(fmt)
         h = ctypes.c_void_p()
         _check(_L.vgen_filter_compile_list(text.encode(), int(case_insensitive), int(fmt), ctypes.byref(h)))
         self._h = h
@@ -583,7 +621,7 @@ class GpuRunner:
                  frames: int = 2, match_cap: int = 4096, timing: bool = True, endo: bool = False, table_bits: int = 0,
                  device_mem_budget_bytes: int = 0):
         # timing: VGEN_FLAG_TIMING — events around every dispatch so that kernel_ms() / dispatch_ms() work
-        # endo: VGEN_FLAG_ENDO — six keys per curve point (vanity searches on compressed-key formats)
+        # endo: VGEN_FLAG_ENDO — six keys per curve point (vanity searches on compressed-key formats; three for Nostr's x-only keys)
         # table_bits / device_mem_budget_bytes: the generator-table width and the device-memory bound of this context (0 = automatic)
         p = _Params(ctypes.sizeof(_Params), device, batch_size, int(fmt), frames, match_cap, (1 if timing else 0) | (2 if endo else 0),
                     table_bits, device_mem_budget_bytes)
@@ -592,8 +630,8 @@ class GpuRunner:
         self._h = h
         b, f, m = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         _L.vgen_get_info(h, ctypes.byref(b), ctypes.byref(f), ctypes.byref(m))
-        self.batch_size, self.frames, self.match_cap, self.format = b.value, f.value, m.value, AddressFormat(int(fmt))
-        self.payload_bytes = 32 if self.format == AddressFormat.P2tr else 20
+        self.batch_size, self.frames, self.match_cap, self.format = b.value, f.value, m.value, _fmt(fmt)
+        self.payload_bytes = 32 if int(self.format) in (int(AddressFormat.P2tr), FORMAT_NOSTR) else 20
         self._pattern = None
 
     def topology(self) -> dict:
@@ -763,7 +801,7 @@ def scan_list(plist: PatternList, config: ScanConfig, runner, per_pattern: int =
         g = res.matches[i]
         a = g.address.decode()
         w = plist.which(a)
-        out.matches.append(ListMatch(a, g.wif.decode(), g.hex.decode(), AddressFormat(g.format), w[0] if w else -1))
+        out.matches.append(ListMatch(a, g.wif.decode(), g.hex.decode(), _fmt(g.format), w[0] if w else -1))
     _L.vgen_scan_result_free(ctypes.byref(res))
     if rc < 0:
         msg = _L.vgen_last_error(runners[0]._h)
@@ -793,7 +831,7 @@ def scan_gpu_with_runner(pattern: str, config: ScanConfig, runner,
                      resumed_operations=res.resumed_operations, complete=bool(res.complete), failed_shards=res.failed_shards)
     for i in range(res.n_matches):
         g = res.matches[i]
-        out.matches.append(GeneratedAddress(g.address.decode(), g.wif.decode(), g.hex.decode(), AddressFormat(g.format)))
+        out.matches.append(GeneratedAddress(g.address.decode(), g.wif.decode(), g.hex.decode(), _fmt(g.format)))
     _L.vgen_scan_result_free(ctypes.byref(res))
     if rc < 0:
         # a failing scan still hands over what its finished batches found (vgen_scan_result is filled, complete = 0)
@@ -815,7 +853,7 @@ def _salt_scan(call, pattern, config, runner, progress_cb, stop) -> ScanResult:
     out = ScanResult(operations=res.operations, elapsed_secs=res.elapsed_secs, complete=bool(res.complete), failed_shards=res.failed_shards)
     for i in range(res.n_matches):
         g = res.matches[i]
-        out.matches.append(GeneratedAddress(g.address.decode(), g.wif.decode(), g.hex.decode(), AddressFormat(g.format)))
+        out.matches.append(GeneratedAddress(g.address.decode(), g.wif.decode(), g.hex.decode(), _fmt(g.format)))
     _L.vgen_scan_result_free(ctypes.byref(res))
     if rc < 0:
         msg = _L.vgen_last_error(runners[0]._h)

@@ -348,6 +348,22 @@ int vgen_key_variant(const uint8_t key_be[32], uint32_t variant, uint8_t out_be[
     return VGEN_OK;
 }
 
+int vgen_nostr_encode(uint32_t kind, const uint8_t data[32], char *out, size_t cap) {
+    if (!data || kind > 1) return VGEN_E_INVALID;
+    return copy_out(vg::nip19_encode(kind ? "nsec" : "npub", data), out, cap);
+}
+
+int vgen_nostr_decode(const char *text, uint32_t *kind, uint8_t out[32]) {
+    if (!text || !kind || !out) return VGEN_E_INVALID;
+    const std::string s(text);
+    for (uint32_t k = 0; k < 2; k++)
+        if (vg::nip19_decode(k ? "nsec" : "npub", s, out)) {
+            *kind = k;
+            return VGEN_OK;
+        }
+    return VGEN_E_INVALID;
+}
+
 int vgen_derive(uint32_t format, const uint8_t key_be[32], char *address, size_t acap, char *wif, size_t wcap) {
     if (!key_be) return VGEN_E_INVALID;
     uint8_t payload[32];

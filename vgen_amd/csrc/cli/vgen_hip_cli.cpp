@@ -72,7 +72,8 @@ int format_id(const std::string &f) {
     if (f == "ethereum-create2") return VGEN_FMT_ETHEREUM_CREATE2;
     if (f == "ethereum-create3") return VGEN_FMT_ETHEREUM_CREATE2;   // no format of its own: a CREATE3 job on a format-7 context (Opts::create3)
     if (f == "p2pkh-uncompressed") return VGEN_FMT_P2PKH_UNCOMPRESSED;
-    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2, ethereum-create3)");
+    if (f == "nostr") return VGEN_FMT_NOSTR;
+    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2, ethereum-create3, nostr)");
 }
 
 const char *format_display(int id) {   // Display for AddressFormat, src/address.rs:48-58
@@ -84,6 +85,7 @@ const char *format_display(int id) {   // Display for AddressFormat, src/address
     case VGEN_FMT_P2TR: return "P2TR";
     case VGEN_FMT_ETHEREUM_CONTRACT: return "Ethereum contract (nonce 0)";   // (no comma: the csv writer keeps eight plain columns)
     case VGEN_FMT_ETHEREUM_CREATE2: return "Ethereum contract (CREATE2)";
+    case VGEN_FMT_NOSTR: return "Nostr (npub)";
     default: return "Ethereum";
     }
 }
@@ -200,7 +202,9 @@ void usage() {
     fprintf(stderr,
             "vgen-hip — MI355X scan engine for the vgen hot path\n\n"
             "  FORMAT: p2pkh (default), p2wpkh, p2sh-p2wpkh, p2tr, p2pkh-uncompressed, ethereum, ethereum-contract (the address of the\n"
-            "          contract the key's account creates with its FIRST transaction, nonce 0; results carry that account as `deployer`)\n"
+            "          contract the key's account creates with its FIRST transaction, nonce 0; results carry that account as `deployer`),\n"
+            "          nostr (the Nostr public key npub1... of NIP-19: Bech32 of the BIP-340 x-only key; results carry the nsec1... secret key\n"
+            "          as `wif` and the key's 32 bytes as `public_key_hex`; unseeded searches test three keys per curve point)\n"
             "  vgen-hip generate -p PATTERN [-f FORMAT] [-i] [-c COUNT] [-o text|json|jsonl|csv|minimal] [--file PATH]\n"
             "                    [--gpu-batch-size N] [--repeat N] [-q] [--seed S] [--devices 0,1,..|all] [--frames F]\n"
             "                    [--frames F]          (dispatches in flight, default 12; several searches on ONE device share it\n"
@@ -776,11 +780,25 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
                 c3_guarded = hex0x(gs, 32);
             }
         }
+        // nostr: the address is the Bech32 of the x-only public key; its 32 bytes in hex beside it
+        std::string pub_hex;
+        if (fmt == VGEN_FMT_NOSTR) {
+            uint32_t kind = 0;
+            uint8_t pub[32];
+            if (vgen_nostr_decode(g.address, &kind, pub) != VGEN_OK || kind != 0) die("a result of a nostr search is no npub");
+            static const char HX[] = "0123456789abcdef";
+            for (int i = 0; i < 32; i++) {
+                pub_hex.push_back(HX[pub[i] >> 4]);
+                pub_hex.push_back(HX[pub[i] & 15]);
+            }
+        }
         uint32_t score = 0;   // (score searches only: every other output stays byte for byte what it was)
         if (score_flt && vgen_score(score_flt, g.address, &score) != VGEN_OK) die("a result of a score search has no score");
         if (o.output == "text") {
             fprintf(w, "=== Match %zu of %zu ===\n", idx + 1, all.size());
             if (create2) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSalt    : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex);
+            else if (!pub_hex.empty()) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nNsec    : %s\nHex     : %s\nPubkey  : %s\n", pattern.c_str(),
+                                               fmt_name.c_str(), g.address, g.wif, g.hex, pub_hex.c_str());
             else fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nWIF     : %s\nHex     : %s\n", pattern.c_str(),
                          fmt_name.c_str(), g.address, g.wif, g.hex);
             if (create3) {
@@ -804,6 +822,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
                 if (!c3_guarded.empty()) fprintf(w, "%s\"guarded_salt\":%s%s,", nl, sp, json_str(c3_guarded).c_str());
             } else if (create2) fprintf(w, "%s\"init_code_hash\":%s%s,", nl, sp, json_str(c2_hash).c_str());
             if (score_flt) fprintf(w, "%s\"score\":%s%u,", nl, sp, score);
+            if (!pub_hex.empty()) fprintf(w, "%s\"public_key_hex\":%s%s,", nl, sp, json_str(pub_hex).c_str());
             fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
                        "\"operations\":%s%llu,%s\"elapsed_secs\":%s%s,%s\"rate\":%s%s%s}\n",
                     nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str(), nl,

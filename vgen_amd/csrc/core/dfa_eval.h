@@ -188,6 +188,23 @@ VG_HD bool dfa_match_bech32(const u32 *blob, const u32 *H, u32 witver) {
     return dfa_accept(v, s);
 }
 
+// Nostr public key (NIP-19): "npub1" + 52 data symbols (256 key bits + 4 zero pad bits) + 6 Bech32 checksum symbols (constant 1,
+// hrp expansion of "npub": bech32_checksum_npub), 63 characters.  The literal head "npub1" is already consumed (blob[2]).
+// payload: the key's eight words in memory order.
+VG_HD bool dfa_match_npub(const u32 *blob, const u32 *payload) {
+    u32 H[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) H[i] = bswap32(payload[i]);
+    const DfaView v = dfa_view(blob);
+    u32 s = blob[2];
+#pragma unroll
+    for (int k = 0; k < 52; k++) s = dfa_step(v, s, bits5<8>(H, k));
+    const u32 chk = bech32_checksum_npub(H);
+#pragma unroll
+    for (int k = 0; k < 6; k++) s = dfa_step(v, s, (chk >> (25 - 5 * k)) & 31u);
+    return dfa_accept(v, s);
+}
+
 // Ethereum: 40 lowercase hex digits after "0x" (DFA compiled case-insensitively for the device).
 VG_HD bool dfa_match_hex40(const u32 *blob, const u32 H[5]) {
     const DfaView v = dfa_view(blob);

@@ -130,4 +130,71 @@ VG_HD bool filter_eval_n(const DevFilter *f, const u32 *payload) {
 
 VG_HD bool filter_eval(const DevFilter *f, const u32 payload[5]) { return filter_eval_n<5>(f, payload); }
 
+// ---- Nostr public keys (NIP-19 npub): Bech32 of the 32-byte x-only key, hrp "npub", no witness-version symbol ----
+// Functions of their own: filter_eval_n is compiled into every older kernel and stays what it is.
+
+// Bech32 checksum (BIP-173 constant 1; 30 bits, first checksum symbol in bits 29..25) of the key given as eight big-endian
+// words: 52 data symbols, the last one carrying one key bit and four zero pad bits.
+VG_HD u32 bech32_checksum_npub(const u32 *H) {
+    u32 c = 1;   // polymod over hrp-expand("npub") = {3, 3, 3, 3, 0, 14, 16, 21, 2}
+    c = bech32_polymod_step(c, 3);
+    c = bech32_polymod_step(c, 3);
+    c = bech32_polymod_step(c, 3);
+    c = bech32_polymod_step(c, 3);
+    c = bech32_polymod_step(c, 0);
+    c = bech32_polymod_step(c, 14);
+    c = bech32_polymod_step(c, 16);
+    c = bech32_polymod_step(c, 21);
+    c = bech32_polymod_step(c, 2);
+#pragma unroll
+    for (int s = 0; s < 52; s++) c = bech32_polymod_step(c, bits5<8>(H, s));
+#pragma unroll
+    for (int i = 0; i < 6; i++) c = bech32_polymod_step(c, 0);
+    return c ^ 1u;
+}
+
+// The prefilter (kinds 2 and 3; a Bech32 string has no range tests) on a key's eight payload words in memory order.  The checksum,
+// for data-part survivors only, goes through the filter's byte tables (32 x 256 words) when it has them.
+VG_HD bool filter_eval_npub(const DevFilter *f, const u32 *payload) {
+    const u32 kind = f->kind;
+    if (kind != DEVF_MASKED) return kind != DEVF_RANGES;   // (ALL; HOST_ALL / DFA are judged elsewhere)
+    u32 H[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) H[i] = bswap32(payload[i]);
+    const u32 n = f->count;
+    const bool need_chk = (f->flags & DEVF_FLAG_BECH32_CHK) != 0;
+    bool any_data = false;
+    for (u32 t = 0; t < n; t++) {
+        const DevFilterTest &T = f->tests[t];
+        u32 diff = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) diff |= (H[i] & T.a[i]) ^ T.b[i];
+        any_data = any_data || (diff == 0);
+    }
+    if (!need_chk || !any_data) return any_data;
+    u32 chk;
+    if (f->chk_lut) {
+        const u32 *lut = f->chk_lut;
+        chk = f->chk_base;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            chk ^= lut[(4 * i + 0) * 256 + (H[i] >> 24)];
+            chk ^= lut[(4 * i + 1) * 256 + ((H[i] >> 16) & 255u)];
+            chk ^= lut[(4 * i + 2) * 256 + ((H[i] >> 8) & 255u)];
+            chk ^= lut[(4 * i + 3) * 256 + (H[i] & 255u)];
+        }
+    } else {
+        chk = bech32_checksum_npub(H);
+    }
+    bool hit = false;
+    for (u32 t = 0; t < n; t++) {
+        const DevFilterTest &T = f->tests[t];
+        u32 diff = (chk & T.chk_mask) ^ T.chk_value;
+#pragma unroll
+        for (int i = 0; i < 8; i++) diff |= (H[i] & T.a[i]) ^ T.b[i];
+        hit = hit || (diff == 0);
+    }
+    return hit;
+}
+
 }  // namespace vg

@@ -15,6 +15,9 @@ enum : int {
     VGF_ETHEREUM_CONTRACT = 6,  // address of the contract the account deploys with nonce 0 (not a format of the reference)
     VGF_ETHEREUM_CREATE2 = 7    // CREATE2 (EIP-1014) address searched by salt: no key, no curve point (not a format of the reference)
 };
+// Nostr public key (NIP-19 npub): the BIP-340 x-only key itself, 32 bytes, no hash (not a format of the reference).  Format 10: the
+// numbers 8 and 9 stay unassigned - every entry point answers them as unknown formats, which callers and the suite rely on.
+constexpr int VGF_NOSTR{10};
 
 // the two formats whose payload is (derived from) the Ethereum account address: hex strings, both coordinates hashed
 constexpr bool vgf_is_eth(int fmt) { return fmt == VGF_ETHEREUM || fmt == VGF_ETHEREUM_CONTRACT; }
@@ -23,6 +26,11 @@ constexpr int vgf_string_format(int fmt) { return (fmt == VGF_ETHEREUM_CONTRACT 
 // the formats whose address string is "0x" + 40 hex digits with EIP-55 casing (vgf_is_eth says how the per-key kernels hash a
 // point and stays what it is: a CREATE2 address has no point behind it)
 constexpr bool vgf_is_hex(int fmt) { return vgf_string_format(fmt) == VGF_ETHEREUM; }
+// payload words of a format: the 32-byte x-only keys (the taproot output key, the Nostr public key) take eight, everything else five
+constexpr int vgf_payload_words(int fmt) { return (fmt == VGF_P2TR || fmt == VGF_NOSTR) ? 8 : 5; }
+// keys tested per curve point on a VGEN_FLAG_ENDO context: the six endomorphism / negation images, or - x-only keys, where (x, y)
+// and (x, -y) are one key - the three images x, beta x, beta^2 x
+constexpr uint32_t vgf_endo_images(int fmt) { return fmt == VGF_NOSTR ? 3u : 6u; }
 
 
 // Device-side prefilter program (built by host/filter.cpp from the pattern's DFA).
@@ -42,7 +50,7 @@ enum : uint32_t {
 constexpr uint32_t DEVF_MAX_TESTS = 64;
 constexpr uint32_t DEVF_FLAG_BECH32_CHK = 1u;   // masked tests also constrain the bech32 checksum
 
-constexpr int DEVF_WORDS = 8;   // payload words a test covers: 5 used for 20-byte payloads, 8 for P2TR
+constexpr int DEVF_WORDS = 8;   // payload words a test covers: 5 used for 20-byte payloads, 8 for P2TR and Nostr keys
 
 struct DevFilterTest {
     uint32_t a[DEVF_WORDS];   // ranges: lo      masked: mask
@@ -104,7 +112,7 @@ struct PtabArgs {
     DevMatch *mrec;
     uint32_t stride;             // slots per image (the context's batch size; a multiple of 8192)
     uint32_t count;              // slots written per image (n of vgen_dispatch_keys, else stride)
-    uint32_t images;             // 6 on an endomorphism dispatch, else 1
+    uint32_t images;             // 6 on an endomorphism dispatch (3 for the x-only Nostr keys), else 1
     uint32_t match_base;
     uint32_t match_cap;
     // (appended: the list kernels' view of the fields above is unchanged)  payload_filter_kernel, instead of a list's table: the
@@ -179,6 +187,9 @@ struct SeqArgs {
     uint32_t *tree2;           // product tree / roots of the lanes' final products, laid out like tree / root
     uint32_t *root2;
     DevSeqQ q[SEQ_MAX_S];      // per-dispatch uniform points, by value (scalar loads from the kernarg segment)
+    // (appended behind q: the older kernels' view of the fields above is unchanged)
+    unsigned long long *hits;  // xonly_bwd_kernel: non-null = the prefilter form - a.filter on the eight words in registers, hit bits into this
+                               // slot-ordered mask (images x n / 64 words, every one written), hit lanes' payloads into a.dump
 };
 
 // Arbitrary-scalar path (keys_fwd_kernel -> seq_inv_kernel -> keys_bwd_kernel): one key per lane, full
@@ -211,6 +222,8 @@ struct KeysArgs {
     uint32_t *xyz;             // scratch: Jacobian results, limb-major [27][groups * KEYS_WG] (X, Y, Z limbs; the taproot stage: X, validity word, Z)
     uint32_t *tree;            // scratch: product-tree nodes [groups][9][KEYS_WG]
     uint32_t *root;            // scratch: tree roots / their inverses [9][groups]
+    // (appended: the older kernels' view of the fields above is unchanged)
+    unsigned long long *hits;  // keys_xonly_kernel: non-null = the prefilter form (as SeqArgs::hits; words beyond ceil(n / 256) * 4 of an image are the caller's to clear)
 };
 
 // ---- score searches (DEVF_SCORE; appended: no structure above changes) ----------------------------------------------------------

@@ -753,6 +753,201 @@ seq_hash_kernel(const SeqArgs args) {
     }
 }
 
+// ---- stage 3 for x-only keys (VGF_NOSTR): the key IS the payload --------------------------------------------------
+//
+// A Nostr public key (NIP-19 npub) is the BIP-340 x-only key: the 32 bytes of x(k*G), no hash, no tweak, not even y.  Per key that
+// is the down-sweep's two products (idx / inv peeling), one product for lambda, one squaring, one canonicalisation and a masked
+// compare — a kernel of its own, so that seq_bwd_kernel stays what it is:
+//   * no y3 (no fe_mul_add), no hash block, no payload_from_point: the payload is fe_to_words(x3) in P2TR's byte order;
+//   * no generated hash block to alternate with, so no priority switching by issue class: the kernel runs at priority 0 like any other;
+//   * !PRE: every payload to args.dump (dump mode, or the frame's device-only buffer in front of the eight-word automaton / list
+//     kernels below).  PRE: the prefilter (kinds 2 and 3, filter_eval_npub) on the eight words IN REGISTERS, as create2_kernel<!DUMP>
+//     does: hit bits into the frame's slot-ordered hit mask, the payloads of hit lanes only, and ptab_compact_kernel<8> makes the
+//     records.  No atomic: match_slot stays with its seven older sites (tests/test_isa_contract.py).  A lane's S slots per sign are S
+//     CONTIGUOUS bits of the mask, so each lane gathers its hit bits over the step loop (bit j of a 16-bit field per sign), and at
+//     the end the 64 / S lanes that share a mask word OR their fields together by lane shuffles and one of them stores the word
+//     (xonly_store_hits): every word of the mask is written exactly once per dispatch, by plain 64-bit stores;
+//   * ENDO: (x, y) and (x, -y) are ONE x-only key, so a point has three images, not six — x, beta x, beta^2 x, the keys of
+//     k, lambda k, lambda^2 k (vgen_key_variant 0 .. 2): two multiplications by beta and two canonicalisations for two more keys.
+//     Image e of key i is reported / dumped at e * n + i.  Nothing of y is parked, and x stays in registers: no LDS beyond the tree.
+// Register budget: the point arithmetic alone (payloads only, one image) fits five waves per SIMD without scratch; at six (80
+// registers) it spills 40 B per lane.  The image loop's second product and the prefilter's eight words and masks spill at five
+// waves, so those forms run at four (the counts: profiles/r05_kernel_resources.txt).
+#ifndef VG_XONLY_WAVES
+#define VG_XONLY_WAVES 5
+#endif
+#ifndef VG_XONLY_WAVES_MATCH   // (the image form)
+#define VG_XONLY_WAVES_MATCH 4
+#endif
+template <bool PRE, bool ENDO>
+struct XonlyWaves {
+    static constexpr int value = (PRE || ENDO) ? VG_XONLY_WAVES_MATCH : VG_XONLY_WAVES;
+};
+
+// PRE: the hit bits one lane gathered for one image (bits 0..15: its +R keys by step j, bits 16..31: its -R keys) into the hit mask.
+// The lane's +R slots are half + u S + j, its -R slots half - (u + 1) S + j: S contiguous bits each, G = 64 / S lanes to a mask word -
+// for -R in descending lane order.  All lanes of the wave reach this together.
+__device__ __forceinline__ void xonly_store_hits(unsigned long long *hits, u32 bits, u32 u, u32 S, u32 half, u32 image_base) {
+    const u32 G = 64u / S, l = u & (G - 1u), field = (1u << S) - 1u;
+    unsigned long long wp = (unsigned long long)(bits & field) << (l * S);
+    unsigned long long wn = (unsigned long long)((bits >> 16) & field) << ((G - 1u - l) * S);
+    for (u32 m = 1; m < G; m <<= 1) {
+        wp |= ((unsigned long long)(u32)__shfl_xor((int)(wp >> 32), (int)m) << 32) | (u32)__shfl_xor((int)wp, (int)m);
+        wn |= ((unsigned long long)(u32)__shfl_xor((int)(wn >> 32), (int)m) << 32) | (u32)__shfl_xor((int)wn, (int)m);
+    }
+    if (l == 0) {
+        hits[(image_base + half + u * S) >> 6] = wp;                    // (u is the first lane of its group: a multiple of G)
+        hits[(image_base + half - (u + G) * S) >> 6] = wn;
+    }
+}
+
+// x: canonical.  out: the 32 big-endian bytes of x in memory order (as p2tr_finish_kernel writes the output key's).
+__device__ __forceinline__ void xonly_payload(const fe &x, u32 out[8]) {
+    u32 xw[8];
+    fe_to_words(x, xw);
+#pragma unroll
+    for (int i = 0; i < 8; i++) out[i] = bswap32(xw[7 - i]);
+}
+
+template <bool PRE, bool ENDO>
+__global__ void __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(XonlyWaves<PRE, ENDO>::value, XonlyWaves<PRE, ENDO>::value)))
+xonly_bwd_kernel(const SeqArgs args) {
+    __shared__ u32 tree[9 * WG];
+    const int tid = threadIdx.x;
+    const u32 S = args.s;
+    const u32 lanes = args.lanes;
+    const u32 u = blockIdx.x * WG + tid;
+
+    const u32 *tg = args.tree + (size_t)blockIdx.x * 9 * WG;
+#pragma unroll
+    for (int i = 0; i < 9; i++) tree[i * WG + tid] = tg[i * WG + tid];
+    __syncthreads();
+    if (tid < 9) tree[tid * WG + 1] = args.root[(size_t)tid * args.groups + blockIdx.x];   // root^-1
+    __syncthreads();
+    // down-sweep: inv[2k] = inv[k] * node[2k+1], inv[2k+1] = inv[k] * node[2k]
+    for (int width = 1; width <= WG / 4; width <<= 1) {
+        if (tid < width) {
+            const int k = width + tid;
+            fe ik, a, b, ia, ib;
+            lds_load_fe(tree, WG, k, ik);
+            lds_load_fe(tree, WG, 2 * k, a);
+            lds_load_fe(tree, WG, 2 * k + 1, b);
+            fe_mul(ia, ik, b);
+            fe_mul(ib, ik, a);
+            lds_store_fe(tree, WG, 2 * k, ia);
+            lds_store_fe(tree, WG, 2 * k + 1, ib);
+        }
+        __syncthreads();
+    }
+    const u32 *pre = args.pre + u;
+    fe inv;
+    {
+        // 1/acc = 1/(acc * sib) * sib, sib = the neighbouring lane's product p_{S-1}
+        fe ip, sib;
+        lds_load_fe(tree, WG, WG / 2 + (tid >> 1), ip);
+#pragma unroll
+        for (int i = 0; i < 9; i++) sib.n[i] = args.pre[(size_t)((S - 1) * 9 + i) * lanes + (u ^ 1u)];
+        fe_mul(inv, ip, sib);
+    }
+    fe rx, ry;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        rx.n[i] = args.rtab[(size_t)i * lanes + u];
+        ry.n[i] = args.rtab[(size_t)(9 + i) * lanes + u];
+    }
+    const u32 half = args.n >> 1;
+    u32 hbits0 = 0, hbits1 = 0, hbits2 = 0;   // PRE: this lane's hit bits per image (xonly_store_hits)
+
+#pragma unroll 1
+    for (int j = (int)S - 1; j >= 0; j--) {
+        const DevSeqQ &q = args.q[j];
+        fe dx, idx;
+#pragma unroll
+        for (int i = 0; i < 9; i++) dx.n[i] = rx.n[i] + q.nqx[i];
+        if (j > 0) {
+            fe pj;
+#pragma unroll
+            for (int i = 0; i < 9; i++) pj.n[i] = pre[(size_t)((j - 1) * 9 + i) * lanes];
+            fe_mul(idx, inv, pj);
+            fe_mul(inv, inv, dx);
+        } else {
+            idx = inv;
+        }
+        // (-R.x and -R.y are recomputed per step, as in seq_bwd_kernel: the empty asm keeps them from being hoisted into 18 registers)
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            asm volatile("" : "+v"(rx.n[i]));
+            asm volatile("" : "+v"(ry.n[i]));
+        }
+        fe nsum;   // -(R.x + Q.x) (magnitude 3), shared by the +R and -R results
+        fe_neg(nsum, rx, 1);
+#pragma unroll
+        for (int i = 0; i < 9; i++) nsum.n[i] += q.nqx[i];
+#pragma unroll 1
+        for (int sgn = 0; sgn < 2; sgn++) {
+            // +R: dy = R.y - Q.y ; -R: dy = -R.y - Q.y
+            fe dy, lam, x3;
+            if (sgn) fe_neg(dy, ry, 1);
+            else dy = ry;
+#pragma unroll
+            for (int i = 0; i < 9; i++) dy.n[i] += q.nqy[i];   // magnitude <= 3
+            fe_mul(lam, dy, idx);
+            fe_sqr_add(x3, lam, nsum);            // lam^2 - R.x - Q.x, weakly normalised
+            fe_canonicalize_product(x3);
+            const u32 index = sgn ? (half - (u + 1) * S + (u32)j) : (half + u * S + (u32)j);
+#pragma unroll 1
+            for (u32 e = 0; e < (ENDO ? 3u : 1u); e++) {
+                if (ENDO && e > 0) {
+                    fe beta;
+                    fe_set_beta(beta);
+                    fe_mul(x3, x3, beta);
+                    fe_canonicalize_product(x3);
+                }
+                u32 pl[8];
+                xonly_payload(x3, pl);
+                const u32 vindex = ENDO ? e * args.n + index : index;
+                u32 *o = args.dump + (size_t)vindex * 8;
+                if (!PRE) {
+#pragma unroll
+                    for (int i = 0; i < 8; i++) o[i] = pl[i];
+                } else {
+                    const bool hit = filter_eval_npub(args.filter, pl);
+                    const u32 bit = (hit ? 1u : 0u) << ((u32)j + (sgn ? 16u : 0u));
+                    hbits0 |= e == 0 ? bit : 0u;     // (selects, not an indexed array: the image loop stays rolled)
+                    if (ENDO) {
+                        hbits1 |= e == 1 ? bit : 0u;
+                        hbits2 |= e == 2 ? bit : 0u;
+                    }
+                    if (hit) {
+#pragma unroll
+                        for (int i = 0; i < 8; i++) o[i] = pl[i];
+                    }
+                }
+            }
+        }
+    }
+    if (PRE) {
+        xonly_store_hits(args.hits, hbits0, u, S, half, 0);
+        if (ENDO) {
+            xonly_store_hits(args.hits, hbits1, u, S, half, args.n);
+            xonly_store_hits(args.hits, hbits2, u, S, half, 2 * args.n);
+        }
+    }
+}
+
+static hipError_t launch_xonly_bwd(const SeqArgs &a, hipStream_t stream) {
+    // a.hits: the prefilter form (kinds 2 - 3; the caller follows with launch_ptab_compact8); else payloads only (dump mode; an
+    // automaton or a list runs behind the kernel: launch_ptab).  S divides 64 (a power of two <= 16): a mask word is whole lanes' fields
+    if (!a.dump || 64u % a.s != 0) return hipErrorInvalidValue;
+    if (a.hits) {
+        if (!a.filter) return hipErrorInvalidValue;
+        if (a.endo) hipLaunchKernelGGL((xonly_bwd_kernel<true, true>), dim3(a.groups), dim3(WG), 0, stream, a);
+        else hipLaunchKernelGGL((xonly_bwd_kernel<true, false>), dim3(a.groups), dim3(WG), 0, stream, a);
+    } else if (a.endo) hipLaunchKernelGGL((xonly_bwd_kernel<false, true>), dim3(a.groups), dim3(WG), 0, stream, a);
+    else hipLaunchKernelGGL((xonly_bwd_kernel<false, false>), dim3(a.groups), dim3(WG), 0, stream, a);
+    return hipGetLastError();
+}
+
 // ---- taproot, stage C: second shared inversion walked back, x(Q), filter ---------------------------------------
 //
 // After seq_bwd_kernel<P2TR> (stage A) and seq_inv_kernel on root2: every lane recovers 1/(product of its 2S
@@ -1310,6 +1505,82 @@ __global__ void __launch_bounds__(KEYS_WG) keys_bwd_kernel(const KeysArgs args) 
     }
 }
 
+// x-only keys (VGF_NOSTR) behind keys_fwd_kernel / seq_inv_kernel: x = X / Z^2 and nothing else — no y, no hash; as
+// xonly_bwd_kernel: !PRE every payload to args.dump (zeroed for "no key"); PRE the prefilter in registers, the wave's ballot
+// into the hit mask (slot = key index: one plain 64-bit store per wave and image, as create2_kernel) and hit lanes' payloads only;
+// ENDO: the three images x, beta x, beta^2 x, image e of key i at e * vstride + i.  Y is read only for keys_fwd_kernel's "no key
+// here" mark (all limbs zero).
+template <bool PRE, bool ENDO>
+__global__ void __launch_bounds__(KEYS_WG) keys_xonly_kernel(const KeysArgs args) {
+    __shared__ u32 tree[9 * KEYS_WG];
+    const int tid = threadIdx.x;
+    const u32 idx = blockIdx.x * KEYS_WG + tid;
+    const u32 lanes = args.groups * KEYS_WG;
+    fe ip;
+    keys_tree_down(tree, args.tree, args.root, args.groups, ip);
+    // 1/Z = 1/(Z * Z_sib) * Z_sib
+    const u32 *in = args.xyz + idx;
+    const u32 *ins = args.xyz + (idx ^ 1u);
+    fe X, zs, zi, zi2, x;
+    u32 ynz = 0;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        X.n[i] = in[(size_t)i * lanes];
+        ynz |= in[(size_t)(9 + i) * lanes];
+        zs.n[i] = ins[(size_t)(18 + i) * lanes];
+    }
+    const bool valid = ynz != 0 && idx < args.n;
+    fe_mul(zi, ip, zs);
+    fe_sqr(zi2, zi);
+    fe_mul(x, X, zi2);
+    fe_canonicalize_product(x);
+#pragma unroll 1
+    for (u32 e = 0; e < (ENDO ? 3u : 1u); e++) {
+        if (ENDO && e > 0) {
+            fe beta;
+            fe_set_beta(beta);
+            fe_mul(x, x, beta);
+            fe_canonicalize_product(x);
+        }
+        u32 pl[8];
+        xonly_payload(x, pl);
+        const u32 vindex = ENDO ? e * args.vstride + idx : idx;
+        u32 *o = args.dump + (size_t)vindex * 8;
+        if (!PRE) {
+            if (idx < args.n) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) o[i] = valid ? pl[i] : 0u;
+            }
+        } else {
+            // (reached by all lanes of the wave together, lanes beyond n included: vstride is a multiple of 64, so a wave is one mask word)
+            const bool hit = valid && filter_eval_npub(args.filter, pl);
+            const unsigned long long mask = __ballot(hit);
+            if ((tid & 63) == 0) args.hits[vindex >> 6] = mask;
+            if (hit) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) o[i] = pl[i];
+            }
+        }
+    }
+}
+
+static hipError_t launch_keys_xonly(const KeysArgs &a, hipStream_t stream, hipEvent_t before_bwd) {
+    if (!a.xyz || !a.tree || !a.root || a.groups != (a.n + KEYS_WG - 1) / KEYS_WG) return hipErrorInvalidValue;
+    if (!a.dump || (a.hits && !a.filter)) return hipErrorInvalidValue;   // (a.hits: the prefilter form; the caller follows with launch_ptab_compact8)
+    hipLaunchKernelGGL(keys_fwd_kernel, dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(seq_inv_kernel, dim3((a.groups + 63) / 64), dim3(64), 0, stream, a.root, a.groups);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (before_bwd && (e = hipEventRecord(before_bwd, stream)) != hipSuccess) return e;
+    if (a.hits && a.endo) hipLaunchKernelGGL((keys_xonly_kernel<true, true>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+    else if (a.hits) hipLaunchKernelGGL((keys_xonly_kernel<true, false>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+    else if (a.endo) hipLaunchKernelGGL((keys_xonly_kernel<false, true>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+    else hipLaunchKernelGGL((keys_xonly_kernel<false, false>), dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+    return hipGetLastError();
+}
+
 template <int FMT>
 static hipError_t launch_keys_fmt(const KeysArgs &a, hipStream_t stream, hipEvent_t before_bwd) {
     const bool full = a.dfa_bytes && !a.dump;
@@ -1816,6 +2087,8 @@ hipError_t launch_keys_scan(int fmt, const KeysArgs &a, hipStream_t stream, hipE
         return launch_keys_fmt<VGF_ETHEREUM_CONTRACT>(a, stream, before_bwd);
     case VGF_P2TR:
         return launch_keys_fmt<VGF_P2TR>(a, stream, before_bwd);
+    case VGF_NOSTR:
+        return launch_keys_xonly(a, stream, before_bwd);
     default:
         return hipErrorInvalidValue;
     }
@@ -1893,6 +2166,8 @@ hipError_t launch_seq_bwd(int fmt, const SeqArgs &a, hipStream_t stream) {
         return launch_bwd<VGF_ETHEREUM_CONTRACT>(a, stream);
     case VGF_P2TR:
         return launch_bwd<VGF_P2TR>(a, stream);
+    case VGF_NOSTR:
+        return launch_xonly_bwd(a, stream);
     default:
         return hipErrorInvalidValue;
     }
@@ -2014,10 +2289,42 @@ __global__ void __launch_bounds__(256) payload_filter_kernel(const PtabArgs a) {
     if ((threadIdx.x & 63u) == 0) a.hits[slot >> 6] = m;
 }
 
+// The eight-word form, for the x-only keys of VGF_NOSTR (a.fmt; the only eight-word format whose filter is deferred): the same
+// geometry and hit mask over 32-byte slots, the npub prefilter (kinds 2 - 3; kind 3 accepts every key) or — FULL — the automaton
+// over the 63-character npub string.
+// A symbol of its own: payload_filter_kernel stays the five-word kernel it is.
+template <bool FULL>
+__global__ void __launch_bounds__(256) payload_filter8_kernel(const PtabArgs a) {
+    extern __shared__ u32 dyn_lds[];
+    if (FULL) {
+        for (u32 i = threadIdx.x; i < a.dfa_bytes / 4; i += 256u) dyn_lds[i] = a.dfa_blob[i];
+        __syncthreads();
+    }
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    const size_t slot = (size_t)blockIdx.y * a.stride + i;
+    bool hit = false;
+    if (i < a.count) {
+        const u32 *p = a.payloads + slot * 8;
+        u32 pl[8], nz = 0;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            pl[k] = p[k];
+            nz |= pl[k];
+        }
+        hit = nz != 0u && (FULL ? dfa_match_npub(dyn_lds, pl) : filter_eval_npub(a.filter, pl));
+    }
+    const unsigned long long m = __ballot(hit);
+    if ((threadIdx.x & 63u) == 0) a.hits[slot >> 6] = m;
+}
+
 hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream) {
     if (a.stride % 256 != 0 || a.count > a.stride || a.images == 0) return hipErrorInvalidValue;
     const dim3 grid(a.stride / 256, a.images);
-    if (a.filter) {   // a DumpOnly format's own filter instead of a list's table
+    if (a.filter && payload_words == 8) {   // the deferred filter of the x-only keys
+        if (a.fmt != VGF_NOSTR || a.dfa_bytes > DFA_MAX_BYTES) return hipErrorInvalidValue;
+        if (a.dfa_bytes) hipLaunchKernelGGL((payload_filter8_kernel<true>), grid, dim3(256), a.dfa_bytes, stream, a);
+        else hipLaunchKernelGGL((payload_filter8_kernel<false>), grid, dim3(256), 0, stream, a);
+    } else if (a.filter) {   // a DumpOnly format's own filter instead of a list's table
         if (payload_words != 5 || a.dfa_bytes > DFA_MAX_BYTES) return hipErrorInvalidValue;
         if (a.dfa_bytes) hipLaunchKernelGGL((payload_filter_kernel<true>), grid, dim3(256), a.dfa_bytes, stream, a);
         else hipLaunchKernelGGL((payload_filter_kernel<false>), grid, dim3(256), 0, stream, a);
@@ -2028,6 +2335,14 @@ hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream)
     if (e != hipSuccess) return e;
     if (payload_words == 8) hipLaunchKernelGGL((ptab_compact_kernel<8>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, a);
     else hipLaunchKernelGGL((ptab_compact_kernel<5>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, a);
+    return hipGetLastError();
+}
+
+// The compaction alone, over eight-word slots: behind a per-key kernel that wrote the hit mask and the hit lanes' payloads itself
+// (xonly_bwd_kernel<PRE>, keys_xonly_kernel<PRE>), as launch_create2 follows create2_kernel<!DUMP> with it.
+hipError_t launch_ptab_compact8(const PtabArgs &a, hipStream_t stream) {
+    if (a.stride % 256 != 0 || a.count > a.stride || a.images == 0 || !a.payloads || !a.hits || !a.mhdr || !a.mrec) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((ptab_compact_kernel<8>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, a);
     return hipGetLastError();
 }
 

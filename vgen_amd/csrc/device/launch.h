@@ -48,6 +48,9 @@ namespace vg {
 // The two kernels of a pattern-list dispatch behind the per-key kernels (which dumped the payloads into a.payloads): lookup
 // of every written slot in the list's interval table into the hit mask, then compaction of the hits into the match ring.
 hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream);
+// The compaction alone over eight-word slots, behind a per-key kernel of the Nostr format that evaluated the prefilter itself
+// (SeqArgs::hits / KeysArgs::hits set): a.payloads / a.hits / a.mhdr / a.mrec and the geometry as for launch_ptab.
+hipError_t launch_ptab_compact8(const PtabArgs &a, hipStream_t stream);
 // A CREATE2 dispatch (VGF_ETHEREUM_CREATE2): one salt per thread, `batch` (a multiple of 256) of them from a.first on, one Keccak block
 // each.  compact == nullptr: every payload goes to a.payloads and nothing else happens - the caller copies the dump out or follows
 // with launch_ptab (pattern list, on-device automaton).  Otherwise the kernel evaluates a.filter itself, writes a.hits and the

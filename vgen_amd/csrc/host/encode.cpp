@@ -1,6 +1,7 @@
 // encode.cpp — see encode.h.
 #include "encode.h"
 
+#include <ctype.h>
 #include <string.h>
 
 #include <mutex>
@@ -257,6 +258,68 @@ std::string segwit_address(const char *hrp, int witver, const uint8_t *prog, siz
     return out;
 }
 
+static uint32_t nip19_polymod_hrp(const char *hrp) {
+    uint32_t c = 1;
+    for (const char *p = hrp; *p; p++) c = polymod_step(c, (uint8_t)*p >> 5);
+    c = polymod_step(c, 0);
+    for (const char *p = hrp; *p; p++) c = polymod_step(c, *p & 31);
+    return c;
+}
+
+std::string nip19_encode(const char *hrp, const uint8_t data[32]) {
+    uint8_t sym[52];
+    uint32_t acc = 0;
+    int bits = 0, n = 0;
+    for (int i = 0; i < 32; i++) {
+        acc = (acc << 8) | data[i];
+        bits += 8;
+        while (bits >= 5) {
+            bits -= 5;
+            sym[n++] = (acc >> bits) & 31;
+        }
+    }
+    sym[n++] = (acc << (5 - bits)) & 31;   // one bit left: the 52nd symbol, four zero pad bits
+    uint32_t c = nip19_polymod_hrp(hrp);
+    for (int i = 0; i < 52; i++) c = polymod_step(c, sym[i]);
+    for (int i = 0; i < 6; i++) c = polymod_step(c, 0);
+    c ^= 1u;
+    std::string out = std::string(hrp) + "1";
+    for (int i = 0; i < 52; i++) out.push_back(BECH32[sym[i]]);
+    for (int i = 0; i < 6; i++) out.push_back(BECH32[(c >> (5 * (5 - i))) & 31]);
+    return out;
+}
+
+bool nip19_decode(const char *hrp, const std::string &text, uint8_t out[32]) {
+    const size_t hl = strlen(hrp);
+    if (text.size() != hl + 1 + 58) return false;
+    bool lower = false, upper = false;
+    for (char ch : text) {
+        lower = lower || (ch >= 'a' && ch <= 'z');
+        upper = upper || (ch >= 'A' && ch <= 'Z');
+    }
+    if (lower && upper) return false;
+    std::string a = text;
+    for (auto &ch : a) ch = (char)tolower((unsigned char)ch);
+    if (a.compare(0, hl, hrp) != 0 || a[hl] != '1') return false;
+    uint32_t c = nip19_polymod_hrp(hrp), acc = 0;
+    int bits = 0, o = 0;
+    for (size_t i = hl + 1; i < a.size(); i++) {
+        const char *q = a[i] ? strchr(BECH32, a[i]) : nullptr;
+        if (!q) return false;
+        const uint32_t v = (uint32_t)(q - BECH32);
+        c = polymod_step(c, v);
+        if (i >= hl + 1 + 52) continue;   // checksum symbols
+        acc = (acc << 5) | v;
+        bits += 5;
+        if (bits >= 8 && o < 32) {
+            bits -= 8;
+            out[o++] = (uint8_t)(acc >> bits);
+        }
+    }
+    if (c != 1u) return false;
+    return (acc & 15u) == 0;   // the four pad bits of the last data symbol
+}
+
 std::string hex_lower(const uint8_t *data, size_t len) {
     static const char HX[] = "0123456789abcdef";
     std::string s;
@@ -302,6 +365,8 @@ std::string address_from_payload(uint32_t format, const uint8_t *payload) {
     case VGF_ETHEREUM_CONTRACT:
     case VGF_ETHEREUM_CREATE2:
         return eip55_address(payload);
+    case VGF_NOSTR:
+        return nip19_encode("npub", payload);
     default:
         return std::string();
     }
@@ -309,6 +374,7 @@ std::string address_from_payload(uint32_t format, const uint8_t *payload) {
 
 std::string key_to_wif(uint32_t format, const uint8_t key_be[32]) {
     if (vgf_is_eth((int)format)) return hex_lower(key_be, 32);
+    if (format == VGF_NOSTR) return nip19_encode("nsec", key_be);
     uint8_t buf[34];
     buf[0] = 0x80;
     memcpy(buf + 1, key_be, 32);
@@ -367,6 +433,9 @@ int payload_from_key(uint32_t format, const uint8_t key_be[32], uint8_t out[32])
         memcpy(out, c, 20);
         return 20;
     }
+    case VGF_NOSTR:   // the BIP-340 x-only key: x itself
+        memcpy(out, pub65 + 1, 32);
+        return 32;
     case VGF_P2TR: {
         // BIP-341 key path, no script tree (address.rs:136-140): the single-source device algorithm
         static std::vector<uint32_t> tab;

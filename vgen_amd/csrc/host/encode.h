@@ -23,12 +23,18 @@ std::string base58_encode(const uint8_t *data, size_t len);
 std::string base58check(const uint8_t *payload, size_t len);
 // hrp + '1' + data(5-bit regrouped, version first) + checksum; bech32 for v0, bech32m for v1+
 std::string segwit_address(const char *hrp, int witver, const uint8_t *prog, size_t len);
+// NIP-19 bare keys: Bech32 (BIP-173, constant 1 - not Bech32m) of 32 bytes under hrp "npub" (x-only public key) or "nsec" (secret
+// key), no witness-version symbol: 52 data symbols (the last one carries one bit and four zero pad bits) + 6 checksum symbols.
+std::string nip19_encode(const char *hrp, const uint8_t data[32]);
+// The strict decoder: `hrp` + "1" + 58 symbols, all lower case or all upper case, zero pad bits, a valid checksum.
+bool nip19_decode(const char *hrp, const std::string &text, uint8_t out[32]);
 std::string eip55_address(const uint8_t addr20[20]);
 std::string hex_lower(const uint8_t *data, size_t len);
 
 // Address string from a device payload; empty string for an unsupported format.
 std::string address_from_payload(uint32_t format, const uint8_t *payload);
-// WIF (compressed unless P2PKH_UNCOMPRESSED); hex for Ethereum (src/address.rs:110)
+// WIF (compressed unless P2PKH_UNCOMPRESSED); hex for Ethereum (src/address.rs:110); nsec1... for Nostr (the scalar as it is: BIP-340
+// signers negate internally)
 std::string key_to_wif(uint32_t format, const uint8_t key_be[32]);
 // Host derivation of the device payload for one key (single-key / verify-style use, tests).
 // Returns the payload length (20 / 32) or 0 for an invalid key.

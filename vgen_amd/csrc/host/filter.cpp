@@ -281,6 +281,8 @@ struct SymSpec {
     unsigned n_data;        // symbols that come from the payload
     unsigned n_chk;         // trailing checksum symbols (Bech32)
     unsigned payload_bits;  // 160, or 256 for P2TR (the last data symbol is then zero-padded)
+    unsigned max_prefix = 12;   // deepest prefix enumeration tried (Nostr keys: all 52 data symbols, so that a long literal prefix is
+                                // a mask over all of its bits - the kernel's compare is eight words wide whatever the depth)
 };
 
 int sym_index(const SymSpec &sp, char c) {
@@ -335,7 +337,7 @@ void derive_symbols(const Dfa &d, const SymSpec &sp, DevFilter &dev, double &sel
     std::vector<Prefix> prefixes;
     size_t pdepth = 0;
     double prefix_sel = 1.0;
-    for (size_t depth = 1; depth <= std::min<size_t>(12, sp.n_data); depth++) {
+    for (size_t depth = 1; depth <= std::min<size_t>(sp.max_prefix, sp.n_data); depth++) {
         std::vector<Prefix> p;
         if (!enumerate_prefixes(d, s, sp.alphabet, depth, 100000, p) || p.size() > DEVF_MAX_TESTS) break;
         double sel_d = 0;
@@ -701,6 +703,27 @@ bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t 
         if (out.dev.kind == DEVF_HOST_ALL && build_dfa_blob(folded, "0x", HEXL, out.dfa_blob)) out.dev.kind = DEVF_DFA;
         break;
     }
+    case VGF_NOSTR: {
+        // npub1 + 52 data symbols (256 key bits + 4 pad bits: the last data symbol is q or s) + 6 Bech32 checksum symbols
+        const SymSpec sp = {"npub1", BECH32, 5, 52, 6, 256, 52};
+        derive_symbols(out.dfa, sp, out.dev, out.selectivity);
+        out.dev.witver = 0;
+        if (out.dev.flags & DEVF_FLAG_BECH32_CHK) {   // the checksum as an affine map of the 32 key bytes, as for P2TR
+            const u32 zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            const u32 base = bech32_checksum_npub(zero);
+            out.chk_lut.assign(32 * 256, 0);
+            for (int i = 0; i < 32; i++)
+                for (u32 b = 0; b < 256; b++) {
+                    u32 H[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                    H[i / 4] = b << (24 - 8 * (i % 4));
+                    out.chk_lut[(size_t)i * 256 + b] = bech32_checksum_npub(H) ^ base;
+                }
+            out.dev.chk_base = base;
+            out.dev.chk_lut = out.chk_lut.data();
+        }
+        if (out.dev.kind == DEVF_HOST_ALL && build_dfa_blob(out.dfa, "npub1", BECH32, out.dfa_blob)) out.dev.kind = DEVF_DFA;
+        break;
+    }
     case VGF_P2TR: {
         // bc1p + 52 data symbols (256 bits + 4 pad bits) + 6 Bech32m checksum symbols
         const SymSpec sp = {"bc1p", BECH32, 5, 52, 6, 256};
@@ -796,11 +819,11 @@ bool list_ranges(const std::string &pattern, bool ci, uint32_t format, uint32_t 
             return false;
         }
         for (auto &r : ranges) out.push_back({top64_of160(r.lo), top64_of160(r.hi), index});
-    } else if (format == VGF_P2WPKH || format == VGF_P2TR || vgf_is_hex((int)format)) {
+    } else if (format == VGF_P2WPKH || format == VGF_P2TR || format == VGF_NOSTR || vgf_is_hex((int)format)) {
         const bool eth = vgf_is_hex((int)format);
-        const char *head = eth ? "0x" : format == VGF_P2TR ? "bc1p" : "bc1q";
+        const char *head = eth ? "0x" : format == VGF_NOSTR ? "npub1" : format == VGF_P2TR ? "bc1p" : "bc1q";
         const char *alphabet = eth ? HEXL : BECH32;
-        const unsigned bits = eth ? 4 : 5, n_data = eth ? 40 : format == VGF_P2TR ? 52 : 32;
+        const unsigned bits = eth ? 4 : 5, n_data = eth ? 40 : (format == VGF_P2TR || format == VGF_NOSTR) ? 52 : 32;
         uint32_t st = 0;
         for (const char *h = head; *h && !d.match_now[st]; h++) st = step(d, st, (unsigned char)*h);
         if (d.match_now[st]) {
@@ -1018,6 +1041,8 @@ bool payload_from_address(uint32_t format, const std::string &address, uint8_t o
             out[i] = (uint8_t)(hv[0] << 4 | hv[1]);
         }
         return true;   // any casing decodes; the patterns' automata judge the string itself
+    } else if (format == VGF_NOSTR) {
+        return nip19_decode("npub", a, out);   // (strict: header, length, case, pad bits, checksum)
     } else if (format == VGF_P2WPKH || format == VGF_P2TR) {
         const size_t n_data = format == VGF_P2TR ? 52 : 32, len = 4 + n_data + 6;
         if (a.size() != len) return false;

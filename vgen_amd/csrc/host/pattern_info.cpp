@@ -3,6 +3,7 @@
 
 #include <ctype.h>
 #include <string.h>
+#include <strings.h>
 
 #include "../device/device_types.h"
 #include "filter.h"
@@ -18,7 +19,8 @@ Charset charset_of(unsigned format) {
     case VGF_P2PKH_UNCOMPRESSED:
     case VGF_P2SH_P2WPKH: return Charset::Base58;
     case VGF_P2WPKH:
-    case VGF_P2TR: return Charset::Bech32;
+    case VGF_P2TR:
+    case VGF_NOSTR: return Charset::Bech32;
     case VGF_ETHEREUM:
     case VGF_ETHEREUM_CONTRACT:
     case VGF_ETHEREUM_CREATE2: return Charset::Hex;
@@ -138,6 +140,12 @@ std::string pattern_invalid_chars(const std::string &p, bool case_insensitive, u
     const Alphabet alpha(alphabet_of(charset_of(format)), case_insensitive);
     OrderedChars bad;
     size_t i = 0;
+    // Nostr: the constant head "npub1" of an anchored pattern is not examined - 'b' and '1' are no data symbols and are valid only there
+    if (format == VGF_NOSTR && p.size() >= 6 && p[0] == '^') {
+        bool head = true;
+        for (size_t k = 0; k < 5; k++) head = head && (case_insensitive ? tolower((unsigned char)p[1 + k]) : p[1 + k]) == "npub1"[k];
+        if (head) i = 6;
+    }
     while (i < p.size()) {
         const unsigned char c = (unsigned char)p[i++];
         if (c == '\\') {
@@ -185,12 +193,15 @@ uint64_t pattern_difficulty(const std::string &p, bool case_insensitive, unsigne
     if (!p.empty() && p[0] == '^') {
         const char *rest = p.c_str() + 1;
         auto starts = [&](const char *lit) { return strncmp(rest, lit, strlen(lit)) == 0; };
+        // Nostr: the head under -i in either case, as pattern_invalid_chars reads it
+        auto starts_ci = [&](const char *lit) { return case_insensitive ? strncasecmp(rest, lit, strlen(lit)) == 0 : starts(lit); };
         switch ((int)format) {
         case VGF_P2PKH:
         case VGF_P2PKH_UNCOMPRESSED: shared = starts("1"); break;
         case VGF_P2SH_P2WPKH: shared = starts("3"); break;
         case VGF_P2WPKH: shared = starts("bc1q") ? 4 : starts("bc1") ? 3 : starts("bc") ? 2 : starts("b"); break;
         case VGF_P2TR: shared = starts("bc1p") ? 4 : starts("bc1") ? 3 : starts("bc") ? 2 : starts("b"); break;
+        case VGF_NOSTR: shared = starts_ci("npub1") ? 5 : starts_ci("npub") ? 4 : starts_ci("npu") ? 3 : starts_ci("np") ? 2 : starts_ci("n"); break;
         case VGF_ETHEREUM:
         case VGF_ETHEREUM_CONTRACT:
         case VGF_ETHEREUM_CREATE2: shared = (starts("0x") || starts("0X")) ? 2 : starts("0"); break;

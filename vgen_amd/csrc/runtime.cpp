@@ -258,7 +258,7 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
         err = "device index out of range";
         return VGEN_E_NODEVICE;
     }
-    if (p->format > VGF_ETHEREUM_CREATE2) {
+    if (p->format > VGF_ETHEREUM_CREATE2 && p->format != VGF_NOSTR) {
         err = "unknown address format";
         return VGEN_E_INVALID;
     }
@@ -280,7 +280,7 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
     c->frames = p->frames ? p->frames : 12;   // the engine's own optimum (the reference's wgpu runner keeps 2, src/gpu.rs:399)
     c->match_cap = p->match_cap ? p->match_cap : 4096;
     c->format = p->format;
-    c->payload_words = p->format == VGF_P2TR ? 8 : 5;
+    c->payload_words = (uint32_t)vgf_payload_words((int)p->format);
     c->timing = (p->flags & VGEN_FLAG_TIMING) != 0;
     c->endo = (p->flags & VGEN_FLAG_ENDO) != 0 && p->format != VGF_P2TR;
     c->S = env_u32("VGEN_SEQ_S", 8);
@@ -432,8 +432,8 @@ int rt_set_match_cap(vgen_ctx *c, uint32_t cap) {
     for (auto &f : c->fr)
         if (f.in_flight) return c->fail(VGEN_E_STATE, "vgen_set_match_cap while a dispatch is in flight");
     if (cap < FIRST_COPY) cap = FIRST_COPY;
-    // a dispatch cannot report more candidates than it tests keys: batch, or six images of each on an ENDO context
-    const uint64_t most = (uint64_t)c->batch * (c->endo ? 6 : 1);
+    // a dispatch cannot report more candidates than it tests keys: batch, or the images of each on an ENDO context
+    const uint64_t most = (uint64_t)c->batch * rt_images(c);
     if (cap > most) cap = (uint32_t)std::min<uint64_t>(most, 0xFFFFFFFFu);
     if (c->d_match_slab && cap == c->match_cap) return VGEN_OK;
     const size_t match_b = up256(match_bytes(cap));
@@ -548,7 +548,7 @@ namespace {
 // `range --puzzle N`, src/lib.rs:519) never uses a third.  The remaining frames get theirs, in one more piece, when one of
 // them is first dispatched in dump mode (ensure_dump_frame).
 int alloc_dump_piece(vgen_ctx *c, uint32_t first, uint32_t n, uint8_t **d_out, uint8_t **h_out) {
-    const size_t per = up256((size_t)c->batch * (c->endo ? 6 : 1) * c->payload_words * sizeof(uint32_t));
+    const size_t per = up256((size_t)c->batch * rt_images(c) * c->payload_words * sizeof(uint32_t));
     uint8_t *d = nullptr, *h = nullptr;
     std::string refused;
     if (!mem_allows(c, (uint64_t)per * n, false, false, &refused)) return c->fail(VGEN_E_NOMEM, "dump buffers: " + refused);
@@ -572,7 +572,7 @@ int alloc_dump_piece(vgen_ctx *c, uint32_t first, uint32_t n, uint8_t **d_out, u
 // 1.5 GB, 24 GB at 2^24 keys per dispatch): at most ~1 GiB worth of frames, never fewer than two — the host-side filter
 // behind a dump runs at a few Mkeys/s, so two dumps in flight already keep it fed.  Reported by vgen_get_resources.
 uint32_t dump_frames_for(const vgen_ctx *c) {
-    const size_t per = up256((size_t)c->batch * (c->endo ? 6 : 1) * c->payload_words * sizeof(uint32_t));
+    const size_t per = up256((size_t)c->batch * rt_images(c) * c->payload_words * sizeof(uint32_t));
     const size_t budget = (size_t)1 << 30;
     return (uint32_t)std::min<size_t>(c->frames, std::max<size_t>(2, budget / per));
 }
@@ -603,13 +603,15 @@ bool list_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind ==
 // list and payload_score_kernel scores the slots; format 7 hashes and scores in create2_score_kernel.  The compaction follows either.
 bool score_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind == DEVF_SCORE; }
 bool deferred_filter(const vgen_ctx *c) {
-    return (c->format == VGF_ETHEREUM_CONTRACT || (c->format == VGF_ETHEREUM_CREATE2 && c->h_filter.kind == DEVF_DFA)) && c->have_filter && !dump_mode(c) &&
+    // ... and so do the x-only Nostr keys (xonly_bwd_kernel's payload form, then the eight-word payload_filter8_kernel<FULL>)
+    return (c->format == VGF_ETHEREUM_CONTRACT || ((c->format == VGF_ETHEREUM_CREATE2 || c->format == VGF_NOSTR) && c->h_filter.kind == DEVF_DFA)) && c->have_filter && !dump_mode(c) &&
            !list_mode(c) && !score_mode(c);
 }
 // ... and evaluates a prefilter (kinds 1 - 3) inside its own kernel: hit mask and the hits' payloads into the frame's list buffers,
 // then the compaction alone.
+// The Nostr per-key kernels do the same (xonly_bwd_kernel<PRE>, keys_xonly_kernel<PRE>): prefilter in registers, an atomic-free hit mask.
 bool inline_filter(const vgen_ctx *c) {
-    return c->format == VGF_ETHEREUM_CREATE2 && c->have_filter && !dump_mode(c) && !list_mode(c) && !deferred_filter(c) && !score_mode(c);
+    return (c->format == VGF_ETHEREUM_CREATE2 || c->format == VGF_NOSTR) && c->have_filter && !dump_mode(c) && !list_mode(c) && !deferred_filter(c) && !score_mode(c);
 }
 
 // The pattern-list buffers of every frame: the payloads of a dispatch (20 B per key, x 6 on an endomorphism context, 32 B for
@@ -617,7 +619,7 @@ bool inline_filter(const vgen_ctx *c) {
 // every frame has them.
 int ensure_list_slab(vgen_ctx *c) {
     if (c->d_list_slab) return VGEN_OK;
-    const size_t slots = (size_t)c->batch * (c->endo ? 6 : 1);
+    const size_t slots = (size_t)c->batch * rt_images(c);
     const size_t pay_b = up256(slots * c->payload_words * sizeof(uint32_t)), hits_b = up256(slots / 8);
     const size_t per = pay_b + hits_b;
     std::string refused;
@@ -663,7 +665,7 @@ int upload_ptab(vgen_ctx *c, const PatternList &L) {
 int enqueue_ptab(vgen_ctx *c, vgen_ctx::Frame &f, uint32_t count, bool endo) {
     PtabArgs p;
     memset(&p, 0, sizeof p);
-    if (score_mode(c)) {
+    if (score_mode(c) || inline_filter(c)) {
         // (the compaction reads nothing but the buffers, the ring and the geometry below)
     } else if (deferred_filter(c)) {
         p.filter = c->d_filter;
@@ -671,7 +673,7 @@ int enqueue_ptab(vgen_ctx *c, vgen_ctx::Frame &f, uint32_t count, bool endo) {
             p.dfa_blob = c->h_filter.dfa_blob;
             p.dfa_bytes = c->h_filter.dfa_bytes;
         }
-        p.fmt = (uint32_t)vgf_string_format((int)c->format);
+        p.fmt = (uint32_t)vgf_string_format((int)c->format);   // (VGF_NOSTR is its own string format: selects the eight-word filter)
     } else {
         p.tab = c->ptab;
     }
@@ -681,7 +683,7 @@ int enqueue_ptab(vgen_ctx *c, vgen_ctx::Frame &f, uint32_t count, bool endo) {
     p.mrec = reinterpret_cast<DevMatch *>(f.d_match + sizeof(DevMatchHeader));
     p.stride = c->batch;
     p.count = count;
-    p.images = endo ? 6 : 1;
+    p.images = endo ? vgf_endo_images((int)c->format) : 1;
     p.match_base = f.match_base;
     p.match_cap = c->match_cap;
     if (score_mode(c)) {
@@ -697,7 +699,8 @@ int enqueue_ptab(vgen_ctx *c, vgen_ctx::Frame &f, uint32_t count, bool endo) {
         HIP_TRY(c, launch_payload_score(sa, p, f.s));
         return VGEN_OK;
     }
-    HIP_TRY(c, launch_ptab(p, (int)c->payload_words, f.s));
+    if (inline_filter(c)) HIP_TRY(c, launch_ptab_compact8(p, f.s));   // (Nostr: the per-key kernel wrote the hit mask itself)
+    else HIP_TRY(c, launch_ptab(p, (int)c->payload_words, f.s));
     return VGEN_OK;
 }
 
@@ -783,7 +786,7 @@ int wait_done(vgen_ctx *c, vgen_ctx::Frame &f) {
 int finish_dispatch(vgen_ctx *c, vgen_ctx::Frame &f, bool dump, uint64_t keys, bool endo) {
     if (c->timing) HIP_TRY(c, hipEventRecord(f.ev_stop, f.s));
     // payload slots of the dump: batch, or — six images per key, image v of key i at v * batch + i — 6 x batch
-    f.dump_slots = (uint64_t)c->batch * (endo ? 6 : 1);
+    f.dump_slots = (uint64_t)c->batch * (endo ? vgf_endo_images((int)c->format) : 1);
     if (dump)
         HIP_TRY(c, hipMemcpyAsync(f.h_dump, f.d_dump, (size_t)f.dump_slots * c->payload_words * sizeof(uint32_t), hipMemcpyDeviceToHost, f.s));
     else
@@ -1282,10 +1285,16 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
     const bool endo_now = c->endo && !(a.dfa_bytes && parks_y && a.dfa_bytes + 2u * 9u * KEYS_WG * 4u > 64u * 1024u);
     a.endo = endo_now ? 1u : 0u;
     a.vstride = c->batch;
-    const bool listed = list_mode(c) || deferred_filter(c) || score_mode(c);
+    const bool inl = inline_filter(c);   // (Nostr contexts only get here: CREATE2 contexts have a dispatch of their own)
+    const bool listed = list_mode(c) || deferred_filter(c) || score_mode(c) || inl;
+    if (inl) {
+        a.hits = f.d_hits;
+        // the kernel writes the mask words of its ceil(n / 256) workgroups; the compaction reads every word of every image
+        if (n < c->batch) HIP_TRY(c, hipMemsetAsync(f.d_hits, 0, (size_t)c->batch * rt_images(c) / 8, f.s));
+    }
     if (dump) {
         if (int rc = ensure_dump_frame(c, (uint32_t)(&f - c->fr.data()))) return rc;
-        if (n < c->batch) HIP_TRY(c, hipMemsetAsync(f.d_dump, 0, (size_t)c->batch * (endo_now ? 6 : 1) * c->payload_words * sizeof(uint32_t), f.s));
+        if (n < c->batch) HIP_TRY(c, hipMemsetAsync(f.d_dump, 0, (size_t)c->batch * (endo_now ? vgf_endo_images((int)c->format) : 1) * c->payload_words * sizeof(uint32_t), f.s));
         a.dump = f.d_dump;
     } else if (listed) {
         a.dump = f.d_list;   // dump mode into the device-only buffer; the list kernels read the first n slots of every image
@@ -1306,7 +1315,7 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
         if (int rc = enqueue_p2tr_stage(c, f, a, n)) return rc;
     if (listed)
         if (int rc = enqueue_ptab(c, f, n, endo_now)) return rc;
-    return finish_dispatch(c, f, dump, endo_now ? (uint64_t)n * 6 : n, endo_now);
+    return finish_dispatch(c, f, dump, endo_now ? (uint64_t)n * vgf_endo_images((int)c->format) : n, endo_now);
 }
 
 }  // namespace
@@ -1378,7 +1387,9 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
         a.lone = others <= c->lone_max_others;
     }
     const bool dump = dump_mode(c);
-    const bool listed = list_mode(c) || deferred_filter(c) || score_mode(c);
+    const bool inl = inline_filter(c);
+    const bool listed = list_mode(c) || deferred_filter(c) || score_mode(c) || inl;
+    if (inl) a.hits = f.d_hits;   // the prefilter form of xonly_bwd_kernel: hit mask + hit lanes' payloads, then the compaction
     if (dump) {
         if (int rc = ensure_dump_frame(c, (uint32_t)(&f - c->fr.data()))) return rc;
         a.dump = f.d_dump;
@@ -1422,7 +1433,7 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
     HIP_TRY(c, launch_seq_bwd((int)c->format, a, f.s));
     if (listed)
         if (int rc = enqueue_ptab(c, f, c->batch, endo_now)) return rc;
-    return finish_dispatch(c, f, dump, endo_now ? (uint64_t)c->batch * 6 : c->batch, endo_now);
+    return finish_dispatch(c, f, dump, endo_now ? (uint64_t)c->batch * vgf_endo_images((int)c->format) : c->batch, endo_now);
 }
 
 int rt_dispatch_keys(vgen_ctx *c, uint32_t frame, const uint8_t *keys_be, uint32_t n) {

@@ -33,7 +33,8 @@ struct vgen_ctx {
     vg::SeqBaseCache base_cache;         // host-side incremental base points (host_ec.h)
     uint32_t payload_words = 5;
     bool timing = false;                 // VGEN_FLAG_TIMING: events around every dispatch
-    bool endo = false;                   // VGEN_FLAG_ENDO (any format but P2TR): six keys per point where the kernels support it
+    bool endo = false;                   // VGEN_FLAG_ENDO (any format but P2TR): six keys per point where the kernels support it (three
+                                         // for the x-only Nostr keys: vg::vgf_endo_images)
 
     uint32_t *d_rtab = nullptr;          // [18][lanes]
     uint32_t *d_gtab = nullptr;          // 8-bit fixed-window generator table (arbitrary-scalar path, P2TR), built on first use
@@ -182,6 +183,9 @@ struct vgen_ctx {
 };
 
 namespace vg {
+
+// Keys a dispatch of this context tests per curve point: 1, or the format's images on a VGEN_FLAG_ENDO context (6; 3 for Nostr keys).
+inline uint32_t rt_images(const vgen_ctx *c) { return c->endo ? vgf_endo_images((int)c->format) : 1u; }
 
 // More frames than hardware queues the runtime provides (GPU_MAX_HW_QUEUES per priority level): streams then share queues.
 inline bool rt_oversubscribed(const vgen_ctx *c) { return c->frames > c->prio_levels * c->hw_queues; }

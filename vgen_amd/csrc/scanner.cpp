@@ -247,7 +247,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
     if (cfg->format != ctx->format) return ctx->fail(VGEN_E_INVALID, "scan format differs from the context's format");
     const bool random_keys = (cfg->flags & VGEN_SCAN_RANDOM_KEYS) != 0;
     if (ctx->endo && !random_keys && (cfg->has_start || cfg->has_end || cfg->seed || cfg->n_shards > 1 || cfg->checkpoint_path))
-        return ctx->fail(VGEN_E_INVALID, "a VGEN_FLAG_ENDO context tests six images of every point, not a contiguous key range: "
+        return ctx->fail(VGEN_E_INVALID, "a VGEN_FLAG_ENDO context tests six images of every point (three for x-only keys), not a contiguous key range: "
                                          "it serves unseeded random scans only (no start / end / seed / shards / checkpoint)");
     // (random keys on an endomorphism context: six keys per draw — the candidate and its lambda / negation images; seeds and
     //  shards keep their meaning there, they name streams of candidates, not ranges)
@@ -272,7 +272,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
         return p;
     };
     bool host_all = flt.dev.kind == DEVF_HOST_ALL;
-    const double keys_per_dispatch = (double)N * (ctx->endo ? 6 : 1);
+    const double keys_per_dispatch = (double)N * rt_images(ctx);
     if (!host_all && flt.selectivity >= 0 && flt.selectivity * keys_per_dispatch * 4 > (double)ctx->match_cap) {
         const uint64_t want = next_pow2((uint64_t)(flt.selectivity * keys_per_dispatch * 4));
         if (want <= N / 2) {
