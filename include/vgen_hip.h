@@ -452,6 +452,39 @@ int vgen_create3_address(const uint8_t factory[20], const uint8_t salt[32], cons
 int vgen_set_create3(vgen_ctx *ctx, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
                      const uint8_t *guard, int32_t guard_len);
 
+/* ---- split-key search: scanning from a caller's public key --------------------------------------------------------------
+ * The requester keeps a secret s and hands over only P = s*G.  A context with P installed as its BASE POINT tests the points
+ * P + k*G for the scalars k its dispatches name and reports the PARTIAL key k: the address belongs to the key (s + k) mod n, which
+ * only the requester can form (vgen_split_combine).  The additive scheme of vanitygen -P and VanitySearch -sp / -rp.
+ * The base is host-side state of the context and serves every key-owned format (0 - 6 and 10), every dispatch entry point, every
+ * filter kind, dumps, VGEN_FLAG_ENDO (the images are those of the POINT P + k*G; an index is still variant * batch_size + i) and
+ * vgen_scan / vgen_scan_multi.  In a dump or a record, a slot whose point is the point at infinity (k*G = -P) holds no key, like a
+ * slot whose scalar is 0 or >= n.
+ * Scans of a context with a base: a result's key is the partial key AS WALKED (no image applied to it: vgen_split_derive /
+ * vgen_split_combine find the image), hex = wif = "0x" + its lowercase hex (never a WIF: a partial key must not look importable),
+ * address = the found address.  Every candidate is re-derived on the host from P + k*G before it becomes a result; one whose payload
+ * differs from the device's is dropped and counted (vgen_split_dropped) - a crafted P can make a walked batch meet the exceptional
+ * cases of the batched additions, and such a scan returns nothing wrong rather than a wrong address.  All contexts of
+ * vgen_scan_multi must share one base (VGEN_E_INVALID).  VGEN_E_UNSUPPORTED with a base set: cfg->checkpoint_path (checkpoints store
+ * keys and re-derive addresses from them), cfg->has_end (key ranges) and vgen_scan_list (lists still work per dispatch). */
+/* Installs the base point: `pub` is a SEC1 public key, 33 bytes compressed (02 / 03) or 65 bytes uncompressed (04); NULL / 0 clears it.
+ * VGEN_E_INVALID for another length or prefix (the hybrid 06 / 07 included), a coordinate >= p or a point not on the curve;
+ * VGEN_E_STATE while a frame is in flight; VGEN_E_UNSUPPORTED on a VGEN_FMT_ETHEREUM_CREATE2 context (salts have no key). */
+int vgen_set_base_point(vgen_ctx *ctx, const uint8_t *pub, size_t len);
+/* The installed base as 65 uncompressed bytes (untouched when none is set) and whether one is set. */
+int vgen_get_base_point(const vgen_ctx *ctx, uint8_t out65[65], int32_t *is_set);
+/* Candidates of this context's scans that the host re-derivation dropped since vgen_create. */
+int vgen_split_dropped(const vgen_ctx *ctx, uint64_t *n);
+/* The address of image `variant` of the point P + partial * G (0 <= partial < n, else VGEN_E_RANGE): images are numbered as
+ * vgen_key_variant numbers them - six, or three for VGEN_FMT_NOSTR; VGEN_E_INVALID beyond that or for a bad `pub`.  VGEN_E_RANGE
+ * when the sum is the point at infinity.  Returns the address's length. */
+int vgen_split_derive(uint32_t format, const uint8_t *pub, size_t len, const uint8_t partial_be[32], uint32_t variant, char *address, size_t cap);
+/* The requester's side: forms (secret + partial) mod n and tries the format's images of it (the image is not stored with a result,
+ * as with VanitySearch -rp); final_be receives the key whose address is `address`, *variant (may be NULL) its image.  VGEN_E_RANGE
+ * for an invalid secret, a partial >= n or a zero sum; VGEN_E_INVALID when no image gives the address. */
+int vgen_split_combine(uint32_t format, const uint8_t secret_be[32], const uint8_t partial_be[32], const char *address, uint8_t final_be[32],
+                       uint32_t *variant);
+
 /* ---- provider patterns (src/provider.rs) -------------------------------------------------------------- */
 
 /* provider::resolve (src/provider.rs:12-52): "boha:b1000:66" / "boha:b1000/66" -> the puzzle's target

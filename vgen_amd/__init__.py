@@ -7,9 +7,9 @@ There is no CPU fallback: importing works anywhere, creating a GpuRunner needs a
 """
 from .api import (AddressFormat, FORMAT_NOSTR, Create2Job, Create3Job, create3_address, create3_proxy_hash, scan_create3, GeneratedAddress, GpuRunner, ListMatch, Pattern, PatternList, ScanConfig, ScanResult, VgenError,
                   abi_version, address_from_payload, contract_address, create2_address, derive, device_count, device_name, keccak256, key_add, key_variant,
-                  key_to_wif, nostr_decode, nostr_encode, npub_from_key, nsec_from_key, random_key, scan_create2, score, library_path, scan_gpu_with_runner, scan_list, ProviderResult, provider_resolve, build_pattern, build_exact_pattern)
+                  key_to_wif, nostr_decode, nostr_encode, npub_from_key, nsec_from_key, random_key, scan_create2, score, split_combine, split_derive, library_path, scan_gpu_with_runner, scan_list, ProviderResult, provider_resolve, build_pattern, build_exact_pattern)
 
 __all__ = ["AddressFormat", "FORMAT_NOSTR", "Create2Job", "Create3Job", "create3_address", "create3_proxy_hash", "scan_create3", "GeneratedAddress", "GpuRunner", "ListMatch", "Pattern", "PatternList", "ScanConfig", "ScanResult", "VgenError",
            "abi_version", "address_from_payload", "contract_address", "create2_address", "keccak256", "scan_create2", "derive", "device_count", "device_name", "key_add", "key_variant",
-           "key_to_wif", "nostr_decode", "nostr_encode", "npub_from_key", "nsec_from_key", "random_key", "score", "library_path", "scan_gpu_with_runner", "scan_list", "ProviderResult", "provider_resolve", "build_pattern",
+           "key_to_wif", "nostr_decode", "nostr_encode", "npub_from_key", "nsec_from_key", "random_key", "score", "split_combine", "split_derive", "library_path", "scan_gpu_with_runner", "scan_list", "ProviderResult", "provider_resolve", "build_pattern",
            "build_exact_pattern"]

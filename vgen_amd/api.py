@@ -176,6 +176,11 @@ _L.vgen_set_create3.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_
 _L.vgen_scan_create3.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
                                  ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint64, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p,
                                  ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_ScanResult)]
+_L.vgen_set_base_point.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
+_L.vgen_get_base_point.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32)]
+_L.vgen_split_dropped.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+_L.vgen_split_derive.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_size_t]
+_L.vgen_split_combine.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32)]
 _L.vgen_device_name.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
 _L.vgen_scan.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(_ScanConfig), _PROGRESS, ctypes.c_void_p,
                          ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_ScanResult)]
@@ -261,6 +266,37 @@ def key_variant(key, variant):
     out = ctypes.create_string_buffer(32)
     _check(_L.vgen_key_variant(_key(key), variant, out))
     return int.from_bytes(out.raw, "big")
+
+
+def _pubkey(pub) -> bytes:
+    """A SEC1 public key as bytes: 33 / 65 bytes, or their hex string (an optional 0x in front)."""
+    if isinstance(pub, str):
+        pub = bytes.fromhex(pub[2:] if pub[:2] in ("0x", "0X") else pub)
+    return bytes(pub)
+
+
+def split_derive(fmt, pub, partial, variant: int = 0) -> Optional[str]:
+    """vgen_split_derive: the address of image `variant` of the point P + partial * G, for the requester's public key `pub` (SEC1,
+    33 or 65 bytes or hex) - what a split-key search reports for the partial key `partial`.  None when the sum is the point at
+    infinity or `partial` is not below n; VgenError for a bad public key, variant or format."""
+    pub, out = _pubkey(pub), ctypes.create_string_buffer(128)
+    rc = _L.vgen_split_derive(int(fmt), pub, len(pub), _key(partial), variant, out, 128)
+    if rc == E_RANGE:
+        return None
+    if rc < 0:
+        raise VgenError(rc, "vgen_split_derive: bad public key, variant or format")
+    return out.value.decode()
+
+
+def split_combine(fmt, secret, partial, address: str):
+    """vgen_split_combine, the requester's side of a split-key search: (final key, variant) with final key = the image `variant` of
+    (secret + partial) mod n whose address is `address`.  VgenError when no image of the sum has that address (a wrong secret, a
+    wrong partial key or a wrong address) or the sum is no key."""
+    out, v = ctypes.create_string_buffer(32), ctypes.c_uint32()
+    rc = _L.vgen_split_combine(int(fmt), _key(secret), _key(partial), address.encode(), out, ctypes.byref(v))
+    if rc < 0:
+        raise VgenError(rc, "vgen_split_combine: no image of secret + partial has this address" if rc == -1 else "vgen_split_combine: secret + partial is not a key, or the format has none")
+    return int.from_bytes(out.raw, "big"), v.value
 
 
 def nostr_encode(kind: str, data: bytes) -> str:
@@ -670,6 +706,26 @@ class GpuRunner:
             blob, n = b"".join(_key(k) for k in keys), len(keys)
         self._n_keys = n
         _check(_L.vgen_dispatch_keys(self._h, frame, blob, n), self._h)
+
+    def set_base(self, pub):
+        """vgen_set_base_point: split-key search - every dispatch of this runner tests P + k * G for the requester's public key P
+        (SEC1, 33 or 65 bytes or hex) and scans report the partial keys k; None clears it.  Only while nothing is in flight."""
+        pub = None if pub is None else _pubkey(pub)
+        _check(_L.vgen_set_base_point(self._h, pub, len(pub) if pub else 0), self._h)
+
+    @property
+    def base(self) -> Optional[bytes]:
+        """vgen_get_base_point: the installed base point as 65 uncompressed bytes, or None."""
+        out, is_set = ctypes.create_string_buffer(65), ctypes.c_int32()
+        _check(_L.vgen_get_base_point(self._h, out, ctypes.byref(is_set)), self._h)
+        return out.raw if is_set.value else None
+
+    @property
+    def split_dropped(self) -> int:
+        """vgen_split_dropped: candidates of this runner's split-key scans that the host's re-derivation refused."""
+        n = ctypes.c_uint64()
+        _check(_L.vgen_split_dropped(self._h, ctypes.byref(n)), self._h)
+        return n.value
 
     def set_create2(self, job: "Create2Job"):
         """vgen_set_create2: the job of an EthereumCreate2 runner."""

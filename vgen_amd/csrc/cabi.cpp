@@ -1,6 +1,7 @@
 // cabi.cpp — the extern "C" surface declared in include/vgen_hip.h.
 #include <stdlib.h>
 #include <string.h>
+#include <strings.h>
 
 #include <string>
 #include <vector>
@@ -467,6 +468,93 @@ int vgen_set_create3(vgen_ctx *ctx, const uint8_t factory[20], const uint8_t pro
     if (!factory || !proxy_init_code_hash || !salt_prefix) return ctx->fail(VGEN_E_INVALID, "vgen_set_create3: null job field");
     if (guard_len < -1 || guard_len > 64 || (guard_len > 0 && !guard)) return ctx->fail(VGEN_E_INVALID, "vgen_set_create3: guard_len is -1 (no guard) or 0 .. 64 bytes");
     return vg::rt_set_create3(ctx, factory, proxy_init_code_hash, salt_prefix, guard, guard_len);
+}
+
+// ---- split-key search ----
+
+int vgen_set_base_point(vgen_ctx *ctx, const uint8_t *pub, size_t len) {
+    if (!ctx) return VGEN_E_INVALID;
+    if (ctx->format == vg::VGF_ETHEREUM_CREATE2)
+        return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: an ethereum-create2 context tests salts - there is no key to split");
+    if (!ctx->base_set) return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: this runtime does not serve split-key dispatches");
+    const bool clear = !pub && len == 0;
+    vg::ge pt;
+    if (!clear && !vg::point_from_sec1(pub, len, pt))
+        return ctx->fail(VGEN_E_INVALID, "vgen_set_base_point: not a secp256k1 public key (33 bytes 02 / 03 + x or 65 bytes 04 + x + y, coordinates "
+                                         "below p, on the curve)");
+    for (auto &f : ctx->fr)
+        if (f.in_flight) return ctx->fail(VGEN_E_STATE, "vgen_set_base_point while a dispatch is in flight");
+    return ctx->base_set(ctx, clear ? nullptr : &pt);
+}
+
+int vgen_get_base_point(const vgen_ctx *ctx, uint8_t out65[65], int32_t *is_set) {
+    if (!ctx || !is_set) return VGEN_E_INVALID;
+    *is_set = ctx->have_base ? 1 : 0;
+    if (ctx->have_base && out65) vg::point_to_sec1(ctx->base_pt, out65);
+    return VGEN_OK;
+}
+
+int vgen_split_dropped(const vgen_ctx *ctx, uint64_t *n) {
+    if (!ctx || !n) return VGEN_E_INVALID;
+    *n = ctx->split_dropped.load(std::memory_order_relaxed);
+    return VGEN_OK;
+}
+
+int vgen_split_derive(uint32_t format, const uint8_t *pub, size_t len, const uint8_t partial_be[32], uint32_t variant, char *address, size_t cap) {
+    if (!pub || !partial_be || !address) return VGEN_E_INVALID;
+    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2) return VGEN_E_UNSUPPORTED;
+    vg::ge base, pt, img;
+    if (variant >= vg::vgf_endo_images((int)format) || !vg::point_from_sec1(pub, len, base)) return VGEN_E_INVALID;
+    vg::Scalar k;
+    vg::scalar_from_be(k, partial_be);
+    if (vg::scalar_cmp_words(k.w, vg::SCALAR_N) >= 0) return VGEN_E_RANGE;
+    if (!vg::point_add_gen(base, k, pt)) return VGEN_E_RANGE;
+    vg::point_image(img, pt, variant);
+    uint8_t payload[32];
+    if (!vg::payload_from_point(format, img, payload)) return VGEN_E_UNSUPPORTED;
+    return copy_out(vg::address_from_payload(format, payload), address, cap);
+}
+
+int vgen_split_combine(uint32_t format, const uint8_t secret_be[32], const uint8_t partial_be[32], const char *address, uint8_t final_be[32],
+                       uint32_t *variant) {
+    if (!secret_be || !partial_be || !address || !final_be) return VGEN_E_INVALID;
+    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2) return VGEN_E_UNSUPPORTED;
+    vg::Scalar s, k, sum;
+    vg::scalar_from_be(s, secret_be);
+    vg::scalar_from_be(k, partial_be);
+    if (!vg::scalar_is_valid(s) || vg::scalar_cmp_words(k.w, vg::SCALAR_N) >= 0) return VGEN_E_RANGE;
+    // (s + k) mod n: both below n, so one conditional subtraction
+    uint64_t c = 0;
+    for (int i = 0; i < 8; i++) {
+        c += (uint64_t)s.w[i] + k.w[i];
+        sum.w[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    if (c || vg::scalar_cmp_words(sum.w, vg::SCALAR_N) >= 0) {
+        int64_t b = 0;
+        for (int i = 0; i < 8; i++) {
+            const int64_t d = (int64_t)sum.w[i] - vg::SCALAR_N[i] + b;
+            sum.w[i] = (uint32_t)d;
+            b = d >> 32;
+        }
+    }
+    if (vg::scalar_is_zero(sum)) return VGEN_E_RANGE;
+    const std::string want(address);
+    for (uint32_t v = 0; v < vg::vgf_endo_images((int)format); v++) {
+        vg::Scalar kv;
+        vg::scalar_variant(kv, sum, v);
+        uint8_t kb[32], payload[32];
+        vg::scalar_to_be(kv, kb);
+        if (!vg::payload_from_key(format, kb, payload)) continue;
+        const std::string got = vg::address_from_payload(format, payload);
+        // (hex addresses: the EIP-55 casing is a checksum, not part of the address)
+        if (vg::vgf_is_hex((int)format) ? got.size() == want.size() && strcasecmp(got.c_str(), want.c_str()) == 0 : got == want) {
+            memcpy(final_be, kb, 32);
+            if (variant) *variant = v;
+            return VGEN_OK;
+        }
+    }
+    return VGEN_E_INVALID;
 }
 
 }  // extern "C"

@@ -52,6 +52,9 @@ struct Opts {
     // -f ethereum-create3: the same salt search through a CREATE3 factory (--deployer is the factory)
     std::string proxy_hash, salt_guard;
     bool has_proxy_hash = false, has_salt_guard = false, salt_guard_hash = false;
+    // split-key search: --base-pubkey (generate), and the requester's `combine`
+    std::string base_pubkey, secret_file, partial;
+    bool has_base = false;
     bool create3() const { return format == "ethereum-create3"; }
     bool any_create3_option() const { return has_proxy_hash || has_salt_guard || salt_guard_hash; }
     bool any_create2_option() const { return has_deployer || has_init_code_hash || has_init_code_file || has_salt_prefix || has_salt_start; }
@@ -234,6 +237,14 @@ void usage() {
             "                    [--salt-prefix 0xHEX] [--salt-start N] [-c COUNT] [-i] [--devices ..] [-o ..]   (CREATE3: the contract the factory's\n"
             "                    proxy deploys, whatever its init code; searches the RAW salt as above.  --salt-guard: the 0 - 64 bytes the factory\n"
             "                    hashes in front of the salt, e.g. the sender's 20 bytes; --salt-guard-hash: it hashes the salt alone)\n"
+            "  vgen-hip generate -p PATTERN --base-pubkey HEX [-f FORMAT] ...   (split-key search for somebody else: HEX is the requester's public\n"
+            "                    key, 33 or 65 bytes; the search walks P + k*G and prints the PARTIAL key k - not a key to anything by itself,\n"
+            "                    never a WIF.  Only the holder of the secret behind HEX can form the final key: `combine`.  Every key-owned\n"
+            "                    format; with --no-endo, --seed, --random-keys, --devices, -c, score: patterns and every writer.  Not with\n"
+            "                    --checkpoint, --patterns-file or range: unsupported for split-key searches)\n"
+            "  vgen-hip combine --secret-file PATH --partial HEX --address ADDR [-f FORMAT]   (the requester's side: PATH holds the secret, 32\n"
+            "                    bytes or 64 hex digits - never on the command line; prints the final key (secret + partial) mod n, under the\n"
+            "                    image that gives ADDR, as the format prints keys; fails if no image of the sum has that address)\n"
             "  vgen-hip generate --patterns-file FILE [--per-pattern N] ...   (instead of -p: one start-anchored prefix per line,\n"
             "                    one scan; N results per pattern (default 1, 0 = unbounded), -c caps the total (default: none);\n"
             "                    each result's pattern field is the lowest-index line it satisfies.  range takes it too)\n"
@@ -258,7 +269,7 @@ Opts parse(int argc, char **argv) {
                                                   "--seed", "--devices", "--frames", "--checkpoint", "--range", "--puzzle", "--key", "--address",
                                                   "--prefix-length", "--provider-table", "--threads", "--backend", "--cpu-batch-size", "--table-bits-max",
                                                   "--mem-budget-gib", "--patterns-file", "--per-pattern", "--deployer", "--init-code-hash", "--init-code-file",
-                                                  "--salt-prefix", "--salt-start", "--proxy-init-code-hash", "--salt-guard"};
+                                                  "--salt-prefix", "--salt-start", "--proxy-init-code-hash", "--salt-guard", "--base-pubkey", "--secret-file", "--partial"};
     static const char short_with_value[] = "pfcorkaltT";
     std::vector<std::string> args;
     bool next_is_value = false;
@@ -337,6 +348,9 @@ Opts parse(int argc, char **argv) {
         else if (a == "--proxy-init-code-hash") { o.proxy_hash = val(); o.has_proxy_hash = true; }
         else if (a == "--salt-guard") { o.salt_guard = val(); o.has_salt_guard = true; }
         else if (a == "--salt-guard-hash") o.salt_guard_hash = true;
+        else if (a == "--base-pubkey") { o.base_pubkey = val(); o.has_base = true; }
+        else if (a == "--secret-file") o.secret_file = val();
+        else if (a == "--partial") o.partial = val();
         else if (a == "-t" || a == "--threads" || a == "--backend" || a == "--cpu-batch-size") (void)val();   // accepted, not applicable
         else if (a == "-h" || a == "--help") { usage(); exit(0); }
         else die("unexpected argument '" + a + "'");
@@ -653,6 +667,21 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         warn_impossible_pattern(pattern, o.ignore_case, fmt);
     }
 
+    // --base-pubkey: a split-key search, checked before any device is opened
+    uint8_t base_pub[65];
+    int base_len = 0;
+    if (o.has_base) {
+        if (create2) die("the argument '--base-pubkey' cannot be used with '-f " + o.format + "' (a salt search has no key to split)");
+        if (has_range) die("the argument '--base-pubkey' cannot be used with 'range': key ranges are not supported for split-key searches");
+        if (!o.checkpoint.empty()) die("the argument '--base-pubkey' cannot be used with '--checkpoint': checkpoints are not supported for split-key searches");
+        if (list) die("the argument '--base-pubkey' cannot be used with '--patterns-file': pattern lists are not supported for split-key searches");
+        base_len = parse_hex_bytes(o.base_pubkey, base_pub, sizeof base_pub);
+        char probe[128];
+        const uint8_t zero[32] = {0};
+        if ((base_len != 33 && base_len != 65) || vgen_split_derive((uint32_t)fmt, base_pub, (size_t)base_len, zero, 0, probe, sizeof probe) < 0)
+            die("--base-pubkey must be a secp256k1 public key in hex: 33 bytes (02 / 03 ..) or 65 bytes (04 ..)");
+    }
+
     std::vector<int> devs = parse_devices(o.devices);
     std::vector<vgen_ctx *> ctxs;
     for (int d : devs) {
@@ -670,7 +699,14 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         if (!o.no_endo && fmt != 3 && !create2 && (o.random_keys || (!has_range && !o.seed && o.checkpoint.empty()))) p.flags |= VGEN_FLAG_ENDO;
         vgen_ctx *c = nullptr;
         if (vgen_create(&p, &c) != VGEN_OK) die(std::string("GPU initialization failed: ") + vgen_last_error(nullptr));
+        if (o.has_base && vgen_set_base_point(c, base_pub, (size_t)base_len) != VGEN_OK) die(vgen_last_error(c));
         ctxs.push_back(c);
+    }
+    std::string base_hex;   // (as given, lower case)
+    for (int i = 0; i < base_len; i++) {
+        char t[3];
+        snprintf(t, sizeof t, "%02x", base_pub[i]);
+        base_hex += t;
     }
 
     vgen_scan_config cfg;
@@ -756,6 +792,17 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         const std::string pattern = list ? list_pattern_of(list, g.address) : pattern_arg;
         // ethereum-contract: the address found is the contract's; the key controls the account that has to deploy it
         char deployer[128] = "";
+        // split-key search: the key is the partial key as walked; which image of P + k*G has the address is found here
+        int variant = -1;
+        if (o.has_base) {
+            char a[128];
+            for (uint32_t v = 0; v < (fmt == VGEN_FMT_NOSTR ? 3u : 6u) && variant < 0; v++)
+                if (vgen_split_derive((uint32_t)fmt, base_pub, (size_t)base_len, g.key, v, a, sizeof a) > 0 && strcmp(a, g.address) == 0) variant = (int)v;
+            if (variant < 0) die("a result of a split-key search is no image of its point");
+            // (ethereum-contract: the deploying account is the one of the FINAL key - the same image of the point)
+            if (fmt == VGEN_FMT_ETHEREUM_CONTRACT && vgen_split_derive(VGEN_FMT_ETHEREUM, base_pub, (size_t)base_len, g.key, (uint32_t)variant, deployer, sizeof deployer) < 0)
+                die("a result of a split-key search has no account");
+        } else
         if (fmt == VGEN_FMT_ETHEREUM_CONTRACT && vgen_derive(VGEN_FMT_ETHEREUM, g.key, deployer, sizeof deployer, nullptr, 0) != VGEN_OK)
             die("malformed or out-of-range secret key");
         // ethereum-create2: the "key" is the salt; the address exists only for this deployer and this init code
@@ -797,7 +844,12 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         if (o.output == "text") {
             fprintf(w, "=== Match %zu of %zu ===\n", idx + 1, all.size());
             if (create2) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSalt    : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex);
-            else if (!pub_hex.empty()) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nNsec    : %s\nHex     : %s\nPubkey  : %s\n", pattern.c_str(),
+            else if (o.has_base) {
+                // a partial key: no key to anything without the secret behind the base public key (vgen-hip combine)
+                fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nPartial key : %s\nBase pubkey : %s\nVariant : %d\n", pattern.c_str(), fmt_name.c_str(),
+                        g.address, g.hex, base_hex.c_str(), variant);
+                if (!pub_hex.empty()) fprintf(w, "Pubkey  : %s\n", pub_hex.c_str());
+            } else if (!pub_hex.empty()) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nNsec    : %s\nHex     : %s\nPubkey  : %s\n", pattern.c_str(),
                                                fmt_name.c_str(), g.address, g.wif, g.hex, pub_hex.c_str());
             else fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nWIF     : %s\nHex     : %s\n", pattern.c_str(),
                          fmt_name.c_str(), g.address, g.wif, g.hex);
@@ -823,9 +875,13 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             } else if (create2) fprintf(w, "%s\"init_code_hash\":%s%s,", nl, sp, json_str(c2_hash).c_str());
             if (score_flt) fprintf(w, "%s\"score\":%s%u,", nl, sp, score);
             if (!pub_hex.empty()) fprintf(w, "%s\"public_key_hex\":%s%s,", nl, sp, json_str(pub_hex).c_str());
-            fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
+            // split-key search: the partial key, the base it belongs to and the image - and no wif: a partial key is not importable
+            if (o.has_base) fprintf(w, "%s\"partial_key_hex\":%s%s,%s\"base_public_key\":%s%s,%s\"variant\":%s%d,", nl, sp, json_str(g.hex + 2).c_str(), nl, sp,
+                                    json_str(base_hex).c_str(), nl, sp, variant);
+            else fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,", nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str());
+            fprintf(w, "%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
                        "\"operations\":%s%llu,%s\"elapsed_secs\":%s%s,%s\"rate\":%s%s%s}\n",
-                    nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str(), nl,
+                    nl,
                     sp, json_str(fmt_name).c_str(), nl, sp, json_str(pattern).c_str(), nl, sp,
                     (unsigned long long)total_ops, nl, sp, json_f64(total_secs).c_str(), nl, sp, json_f64(rate).c_str(),
                     pretty ? "\n" : "");
@@ -930,6 +986,49 @@ int main(int argc, char **argv) {
         for (int i = 0; i < 32; i++) start_zero = start_zero && start[i] == 0;
         if (start_zero) start[31] = 1;   // key 0 is not a key: the CPU path skips it (scanner.rs:294-295)
         return run_search(o, o.has_pattern ? o.pattern : ".", true, start, end);   // default pattern, lib.rs:519
+    }
+    if (o.cmd == "combine") {
+        // The requester's side of a split-key search: final key = (secret + partial) mod n under the image that gives the address.
+        // The secret comes from a file (32 raw bytes, or 64 hex digits with an optional 0x and trailing white space), never from
+        // the command line, where every user of the machine could read it.
+        if (o.secret_file.empty() || o.partial.empty() || o.address.empty())
+            die("the following required arguments were not provided: --secret-file <PATH> --partial <HEX> --address <ADDRESS>");
+        const int fmt = format_id(o.format);
+        if (fmt == VGEN_FMT_ETHEREUM_CREATE2) die("'-f " + o.format + "' has no keys to combine");
+        FILE *f = fopen(o.secret_file.c_str(), "rb");
+        if (!f) die("cannot read secret file '" + o.secret_file + "'");
+        char buf[256];
+        const size_t n = fread(buf, 1, sizeof buf, f);
+        fclose(f);
+        uint8_t secret[32], partial[32], final_key[32];
+        if (n == 32) {
+            memcpy(secret, buf, 32);
+        } else {
+            std::string h(buf, n);
+            while (!h.empty() && isspace((unsigned char)h.back())) h.pop_back();
+            if (h.compare(0, 2, "0x") == 0 || h.compare(0, 2, "0X") == 0) h = h.substr(2);
+            if (h.size() != 64 || !parse_hex_key(h, secret)) die("the secret file must hold 32 bytes, or 64 hex digits");
+        }
+        std::string ph = o.partial;
+        if (ph.compare(0, 2, "0x") == 0 || ph.compare(0, 2, "0X") == 0) ph = ph.substr(2);
+        if (!parse_hex_key(ph, partial)) die("--partial must be a partial key in hex (at most 64 digits)");
+        uint32_t variant = 0;
+        const int rc = vgen_split_combine((uint32_t)fmt, secret, partial, o.address.c_str(), final_key, &variant);
+        memset(secret, 0, sizeof secret);
+        memset(buf, 0, sizeof buf);
+        if (rc == VGEN_E_RANGE) die("the secret is not a valid key, or secret + partial is not one");
+        if (rc != VGEN_OK) die("no image of secret + partial has the address " + o.address + ": wrong secret file, partial key, address or format");
+        char addr[128], wif[128];
+        if (vgen_derive((uint32_t)fmt, final_key, addr, sizeof addr, wif, sizeof wif) != VGEN_OK) die("malformed or out-of-range secret key");
+        std::string hex;
+        for (int i = 0; i < 32; i++) {
+            char b[3];
+            snprintf(b, sizeof b, "%02x", final_key[i]);
+            hex += b;
+        }
+        printf("Format  : %s\nAddress : %s\n%s: %s\nHex     : %s\nVariant : %u\n", format_display(fmt), addr, fmt == VGEN_FMT_NOSTR ? "Nsec    " : "WIF     ", wif,
+               hex.c_str(), variant);
+        return 0;
     }
     if (o.cmd == "list-gpus") {
         int n = 0;

@@ -224,6 +224,10 @@ struct KeysArgs {
     uint32_t *root;            // scratch: tree roots / their inverses [9][groups]
     // (appended: the older kernels' view of the fields above is unchanged)
     unsigned long long *hits;  // keys_xonly_kernel: non-null = the prefilter form (as SeqArgs::hits; words beyond ceil(n / 256) * 4 of an image are the caller's to clear)
+    // (appended behind hits, the same way)  split-key dispatches: has_base != 0 = keys_fwd_base_kernel runs in keys_fwd_kernel's place
+    // and lane i's point is base_pt + k_i * G (canonical limbs); the infinity k_i * G = -base_pt is a "no key" slot
+    uint32_t has_base;
+    DevAffine base_pt;
 };
 
 // ---- score searches (DEVF_SCORE; appended: no structure above changes) ----------------------------------------------------------

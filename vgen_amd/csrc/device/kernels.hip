@@ -1355,6 +1355,78 @@ __global__ void __launch_bounds__(KEYS_WG) keys_fwd_kernel(const KeysArgs args) 
     if (tid < 9) args.root[(size_t)tid * args.groups + blockIdx.x] = tree[tid * KEYS_WG + 1];
 }
 
+// keys_fwd_kernel for split-key dispatches (KeysArgs::has_base): the lane's point is P + k*G for the caller's public key
+// P = args.base_pt.  That sum has the exceptional cases the window accumulation never meets, so it goes through the complete mixed
+// addition: k*G = P is a doubling, k*G = -P the point at infinity.  Infinity is one more "no key": Y parked as 0 like an invalid
+// scalar's, and Z parked as ONE, never 0 - a zero in the product tree would destroy the inversion of all 256 lanes of the
+// workgroup, beginning with the pair lane idx ^ 1 that shares the leaf product.  (An invalid scalar's stand-in k = 1 can meet
+// G = -P the same way and is parked by the same rule.)  A kernel of its own, its text beside the plain one's: as a shared template
+// body the plain kernel came out of the compiler with other registers, and its instructions are what every keys dispatch without
+// a base has been measured with.
+__global__ void __launch_bounds__(KEYS_WG) keys_fwd_base_kernel(const KeysArgs args) {
+    __shared__ u32 tree[9 * KEYS_WG];
+    const int tid = threadIdx.x;
+    const u32 idx = blockIdx.x * KEYS_WG + tid;
+    const u32 lanes = args.groups * KEYS_WG;
+    u32 k[8];
+    bool valid = keys_load_scalar(args, idx, k);
+
+    gej acc;
+    {
+        gej kg;
+        ec_mul_gen_tables(kg, k, GenTables{args.gtab, args.gtab16, args.gtab_bits});
+        ge base;
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            base.x.n[i] = args.base_pt.x[i];
+            base.y.n[i] = args.base_pt.y[i];
+        }
+        gej_add_ge(acc, kg, base);
+    }
+    if (acc.inf) {
+        fe_set_one(acc.z);   // (x = y = 0: gej_set_infinity)
+        valid = false;
+    }
+
+    // "no key here" travels to keys_bwd_kernel as Y = 0 (all limbs): no finite point of this odd-order group has y = 0, so
+    // the scalar (an upload, or a SHA-256 in the random-stream mode) is not loaded / drawn and range-checked a second time
+    u32 *o = args.xyz + idx;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        o[(size_t)i * lanes] = acc.x.n[i];
+        o[(size_t)(9 + i) * lanes] = valid ? acc.y.n[i] : 0u;
+        o[(size_t)(18 + i) * lanes] = acc.z.n[i];
+    }
+    // product tree of the Z's (never zero: 0 < k < n, infinity parked as 1); the leaf level is exchanged by a lane shuffle
+    fe sib, pair;
+    shfl_xor_fe(sib, acc.z, 1);
+    fe_mul(pair, acc.z, sib);
+    if ((tid & 1) == 0) lds_store_fe(tree, KEYS_WG, KEYS_WG / 2 + (tid >> 1), pair);
+    __syncthreads();
+#pragma unroll 1
+    for (int width = KEYS_WG / 4; width >= 1; width >>= 1) {
+        if (tid < width) {
+            const int kk = width + tid;
+            fe a, b, p;
+            lds_load_fe(tree, KEYS_WG, 2 * kk, a);
+            lds_load_fe(tree, KEYS_WG, 2 * kk + 1, b);
+            fe_mul(p, a, b);
+            lds_store_fe(tree, KEYS_WG, kk, p);
+        }
+        __syncthreads();
+    }
+    u32 *tg = args.tree + (size_t)blockIdx.x * 9 * KEYS_WG;
+#pragma unroll
+    for (int i = 0; i < 9; i++) tg[i * KEYS_WG + tid] = tree[i * KEYS_WG + tid];
+    if (tid < 9) args.root[(size_t)tid * args.groups + blockIdx.x] = tree[tid * KEYS_WG + 1];
+}
+
+// the first stage of a keys dispatch: the plain kernel, or its split-key twin when the dispatch carries a base point
+static void launch_keys_fwd(const KeysArgs &a, hipStream_t stream) {
+    if (a.has_base) hipLaunchKernelGGL(keys_fwd_base_kernel, dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+    else hipLaunchKernelGGL(keys_fwd_kernel, dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+}
+
 // ENDO (endomorphism contexts; every format but P2TR): the six images of every point, as seq_bwd_kernel<FMT, FULL, ENDO> tests them
 // — six keys hashed for one scalar multiplication (k, lambda k, lambda^2 k and their negations; image `variant` of key i is
 // reported / dumped at variant * vstride + i, vstride = the context's batch size).
@@ -1567,7 +1639,7 @@ __global__ void __launch_bounds__(KEYS_WG) keys_xonly_kernel(const KeysArgs args
 static hipError_t launch_keys_xonly(const KeysArgs &a, hipStream_t stream, hipEvent_t before_bwd) {
     if (!a.xyz || !a.tree || !a.root || a.groups != (a.n + KEYS_WG - 1) / KEYS_WG) return hipErrorInvalidValue;
     if (!a.dump || (a.hits && !a.filter)) return hipErrorInvalidValue;   // (a.hits: the prefilter form; the caller follows with launch_ptab_compact8)
-    hipLaunchKernelGGL(keys_fwd_kernel, dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+    launch_keys_fwd(a, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(seq_inv_kernel, dim3((a.groups + 63) / 64), dim3(64), 0, stream, a.root, a.groups);
@@ -1586,7 +1658,7 @@ static hipError_t launch_keys_fmt(const KeysArgs &a, hipStream_t stream, hipEven
     const bool full = a.dfa_bytes && !a.dump;
     if (full && a.dfa_bytes > DFA_MAX_BYTES) return hipErrorInvalidValue;
     if (!a.xyz || !a.tree || !a.root || a.groups != (a.n + KEYS_WG - 1) / KEYS_WG) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(keys_fwd_kernel, dim3(a.groups), dim3(KEYS_WG), 0, stream, a);
+    launch_keys_fwd(a, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(seq_inv_kernel, dim3((a.groups + 63) / 64), dim3(64), 0, stream, a.root, a.groups);

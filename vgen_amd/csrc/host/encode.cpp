@@ -400,6 +400,10 @@ int payload_from_key(uint32_t format, const uint8_t key_be[32], uint8_t out[32])
     if (!scalar_is_valid(k)) return 0;
     ge p;
     if (!host_ec_mul_gen(k, p)) return 0;
+    return payload_from_point(format, p, out);
+}
+
+int payload_from_point(uint32_t format, const ge &p, uint8_t out[32]) {
     uint8_t pub65[65], pub33[33], h[20], script[22], kk[32];
     pub65[0] = 0x04;
     fe_to_be32(p.x, pub65 + 1);
@@ -454,6 +458,117 @@ int payload_from_key(uint32_t format, const uint8_t key_be[32], uint8_t out[32])
     default:
         return 0;
     }
+}
+
+// ---- split-key search ------------------------------------------------------------------------------------------------------
+
+namespace {
+
+// 32 big-endian bytes -> canonical fe; false when the value is >= p
+bool fe_from_be32(fe &r, const uint8_t be[32]) {
+    static const uint32_t P_WORDS[8] = {0xFFFFFC2Fu, 0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    Scalar w;
+    scalar_from_be(w, be);
+    if (scalar_cmp_words(w.w, P_WORDS) >= 0) return false;
+    fe_from_words(r, w.w);
+    return true;
+}
+
+// r = a^((p + 1) / 4), the square root of a when it has one (p = 3 mod 4); the addition chain of fe_inv_fermat up to x223.
+// The caller squares r to find out.
+void fe_sqrt_candidate(fe &r, const fe &a) {
+    fe x2, x3, x6, x9, x11, x22, x44, x88, x176, x220, x223, t1;
+    fe_sqr(x2, a);        fe_mul(x2, x2, a);
+    fe_sqr(x3, x2);       fe_mul(x3, x3, a);
+    x6 = x3;   fe_sqr_n_(x6, 3);    fe_mul(x6, x6, x3);
+    x9 = x6;   fe_sqr_n_(x9, 3);    fe_mul(x9, x9, x3);
+    x11 = x9;  fe_sqr_n_(x11, 2);   fe_mul(x11, x11, x2);
+    x22 = x11; fe_sqr_n_(x22, 11);  fe_mul(x22, x22, x11);
+    x44 = x22; fe_sqr_n_(x44, 22);  fe_mul(x44, x44, x22);
+    x88 = x44; fe_sqr_n_(x88, 44);  fe_mul(x88, x88, x44);
+    x176 = x88; fe_sqr_n_(x176, 88); fe_mul(x176, x176, x88);
+    x220 = x176; fe_sqr_n_(x220, 44); fe_mul(x220, x220, x44);
+    x223 = x220; fe_sqr_n_(x223, 3);  fe_mul(x223, x223, x3);
+    t1 = x223; fe_sqr_n_(t1, 23);   fe_mul(t1, t1, x22);
+    fe_sqr_n_(t1, 6);    fe_mul(t1, t1, x2);
+    fe_sqr_n_(t1, 2);
+    r = t1;
+}
+
+// x^3 + 7, canonical
+void curve_rhs(fe &r, const fe &x) {
+    fe x2, seven;
+    fe_sqr(x2, x);
+    fe_mul(r, x2, x);
+    fe_set_zero(seven);
+    seven.n[0] = 7;
+    fe_add(r, r, seven);
+    fe_normalize(r);
+}
+
+}  // namespace
+
+bool point_from_sec1(const uint8_t *pub, size_t len, ge &out) {
+    if (!pub || (len != 33 && len != 65)) return false;
+    const bool compressed = pub[0] == 0x02 || pub[0] == 0x03;
+    if (len == 33 ? !compressed : pub[0] != 0x04) return false;
+    fe x, y, rhs, y2;
+    if (!fe_from_be32(x, pub + 1)) return false;
+    curve_rhs(rhs, x);
+    if (compressed) {
+        fe_sqrt_candidate(y, rhs);
+        fe_normalize(y);
+        if ((y.n[0] & 1u) != (uint32_t)(pub[0] & 1u)) {
+            fe ny;
+            fe_neg(ny, y, 1);
+            fe_normalize(ny);
+            y = ny;
+        }
+    } else if (!fe_from_be32(y, pub + 33)) {
+        return false;
+    }
+    fe_sqr(y2, y);
+    fe_normalize(y2);
+    if (!fe_equal_canonical(y2, rhs)) return false;   // no square root / not on the curve (y = 0 is on no point of this curve)
+    out.x = x;
+    out.y = y;
+    return true;
+}
+
+void point_to_sec1(const ge &p, uint8_t out65[65]) {
+    out65[0] = 0x04;
+    fe_to_be32(p.x, out65 + 1);
+    fe_to_be32(p.y, out65 + 33);
+}
+
+void point_image(ge &r, const ge &p, uint32_t variant) {
+    // beta, the cube root of unity mod p with lambda * (x, y) = (beta * x, y) (the constant of kernels.hip: fe_set_beta)
+    static const u32 BETA[9] = {0x119501EEu, 0x09CB6143u, 0x1D626570u, 0x0092EA25u, 0x034E99CFu, 0x03CF561Au, 0x1C41B991u, 0x056CAF80u, 0x007AE96Au};
+    fe beta;
+    for (int i = 0; i < 9; i++) beta.n[i] = BETA[i];
+    r = p;
+    for (uint32_t e = 0; e < variant % 3; e++) {
+        fe_mul(r.x, r.x, beta);
+        fe_normalize(r.x);
+    }
+    if (variant >= 3) {
+        fe ny;
+        fe_neg(ny, r.y, 1);
+        fe_normalize(ny);
+        r.y = ny;
+    }
+}
+
+bool point_add_gen(const ge &base, const Scalar &k, ge &out) {
+    gej acc;
+    ge kg;
+    if (host_ec_mul_gen(k, kg)) {
+        gej_from_ge(acc, kg);
+        gej_add_ge(acc, acc, base);   // complete: k*G = base doubles, k*G = -base is the point at infinity
+    } else {
+        gej_from_ge(acc, base);       // k = 0 (mod n)
+    }
+    return ge_from_gej(out, acc);
 }
 
 }  // namespace vg

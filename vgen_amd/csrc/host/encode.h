@@ -10,6 +10,9 @@
 
 #include <string>
 
+#include "../core/ec.h"
+#include "scalar.h"
+
 namespace vg {
 
 void host_sha256(const uint8_t *msg, size_t len, uint8_t out[32]);
@@ -39,5 +42,18 @@ std::string key_to_wif(uint32_t format, const uint8_t key_be[32]);
 // Host derivation of the device payload for one key (single-key / verify-style use, tests).
 // Returns the payload length (20 / 32) or 0 for an invalid key.
 int payload_from_key(uint32_t format, const uint8_t key_be[32], uint8_t out[32]);
+
+// ---- split-key search: the host's side of P + k*G (vgen_set_base_point, vgen_split_derive / vgen_split_combine, make_match) ----
+// The same derivation from a public key: an affine point with canonical coordinates.  Payload length, or 0 (unknown format, or a
+// taproot tweak that is no scalar).
+int payload_from_point(uint32_t format, const ge &p, uint8_t out[32]);
+// SEC1 public key -> point: 33 bytes (02 / 03 + x) or 65 bytes (04 + x + y).  false for any other length or prefix (the hybrid 06 /
+// 07 included), a coordinate >= p, an x whose x^3 + 7 has no square root, or a y off the curve.
+bool point_from_sec1(const uint8_t *pub, size_t len, ge &out);
+void point_to_sec1(const ge &p, uint8_t out65[65]);
+// Image `variant` of a point, numbered as scalar_variant numbers a key's: (beta^(variant % 3) x, variant >= 3 ? -y : y).
+void point_image(ge &r, const ge &p, uint32_t variant);
+// out = base + k*G for any 256-bit k (taken mod n; k = 0 gives the base itself).  false when the sum is the point at infinity.
+bool point_add_gen(const ge &base, const Scalar &k, ge &out);
 
 }  // namespace vg

@@ -239,12 +239,17 @@ void fill_ahead(SeqBaseCache &c) {
     c.ahead_n = K;
 }
 
-bool seq_points_full(const Scalar &kb, uint32_t S, ge *out) {
+// (`add`, optional: every point carries it - the complete mixed addition: kb*G = add doubles, kb*G = -add is the point at infinity)
+bool seq_points_full(const Scalar &kb, uint32_t S, ge *out, const ge *add) {
     ge base, g;
     if (!host_ec_mul_gen(kb, base)) return false;
     ge_generator(g);
     gej jac[32];
     gej_from_ge(jac[0], base);
+    if (add) {
+        gej_add_ge(jac[0], jac[0], *add);
+        if (jac[0].inf) return false;
+    }
     for (uint32_t j = 1; j < S; j++) {
         gej_add_ge(jac[j], jac[j - 1], g);
         if (jac[j].inf) return false;
@@ -255,9 +260,15 @@ bool seq_points_full(const Scalar &kb, uint32_t S, ge *out) {
 
 }  // namespace
 
-bool host_seq_points(SeqBaseCache &c, const Scalar &kb, uint32_t S, ge *out) {
+bool host_seq_points(SeqBaseCache &c, const Scalar &kb, uint32_t S, ge *out, const ge *base) {
     bool done = false;
     bool stride_repeated = false;
+    // the cached points belong to one base point (or to none): a change invalidates them, the stride point delta*G stays good
+    if (c.valid && (c.has_base != (base != nullptr) ||
+                    (base && (memcmp(c.base.x.n, base->x.n, sizeof base->x.n) != 0 || memcmp(c.base.y.n, base->y.n, sizeof base->y.n) != 0)))) {
+        c.valid = false;
+        c.ahead_n = c.ahead_pos = 0;
+    }
     if (c.valid && c.S == S && c.ahead_pos < c.ahead_n && c.dvalid) {
         // the look-ahead holds kb_prev + delta next: hand it out if that is what is asked for
         Scalar expect;
@@ -295,11 +306,13 @@ bool host_seq_points(SeqBaseCache &c, const Scalar &kb, uint32_t S, ge *out) {
             if (c.dvalid) done = batch_affine_add(c.q, c.dpt, S, out);
         }
     }
-    if (!done && !seq_points_full(kb, S, out)) {
+    if (!done && !seq_points_full(kb, S, out, base)) {
         c.valid = false;
         return false;
     }
     c.valid = true;
+    c.has_base = base != nullptr;
+    if (base) c.base = *base;
     c.S = S;
     c.kb = kb;
     for (uint32_t j = 0; j < S; j++) c.q[j] = out[j];

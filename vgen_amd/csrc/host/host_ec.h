@@ -45,10 +45,15 @@ struct SeqBaseCache {
     ge mult[LOOK];        // (i+1) * delta * G
     uint32_t ahead_n = 0, ahead_pos = 0;
     ge ahead[LOOK][32];
+    // split-key walks: the base point the cached points carry (q[j] = (kb + j)*G + base); another base, or none, starts afresh
+    bool has_base = false;
+    ge base{};
 };
 
 // out[j] = (kb + j)*G for j < S.  false if any point is the point at infinity (kb + j == 0 mod n).
-bool host_seq_points(SeqBaseCache &cache, const Scalar &kb, uint32_t S, ge *out);
+// `base` (split-key walks, optional): out[j] = (kb + j)*G + base.  The base is folded in where the cache is seeded - one complete mixed
+// addition, no inversion beyond the seed's own - and advancing by delta*G then works as it does without one.
+bool host_seq_points(SeqBaseCache &cache, const Scalar &kb, uint32_t S, ge *out, const ge *base = nullptr);
 
 }  // namespace vg
 

@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -24,6 +25,9 @@ struct BatchKeys {
     RndSeed seed{};
     uint64_t first_index = 0;
     uint32_t stream = 0;
+    // split-key scans (a context with a base point): the base P the batch was dispatched under, and where refused candidates are counted
+    const ge *base = nullptr;
+    std::atomic<uint64_t> *dropped = nullptr;
 };
 
 // A confirmed match as the scan loop carries it: the private key and the address string.  WIF and hex are rendered when
@@ -107,6 +111,29 @@ inline bool make_match(const vgen_filter &flt, uint32_t format, const BatchKeys 
     } else if (scalar_add_u64(k, bk.start, index) || !scalar_is_valid(k)) {
         return false;                                                   // increment_key -> None
     }
+    if (bk.base) {
+        // Split-key scan: the result is the PARTIAL key as walked (no image applied: the address is image `variant` of the point
+        // P + k*G, and only the requester can apply it to s + k).  The payload is re-derived here from P + k*G with the host's
+        // complete addition and the single-source hashes, and a candidate whose payload differs from the device's is dropped and
+        // counted: the walk's "no exceptional cases because k0 + N + S < n" is a statement about the effective scalar s + k,
+        // which the host does not know - a crafted P makes one workgroup's batched additions meet Q_j = +/-R_u and garbles its
+        // payloads.  One point operation per MATCH, not per key.
+        ge pt, img;
+        uint8_t mine[32] = {0};
+        bool same = scalar_is_valid(k) && point_add_gen(*bk.base, k, pt);
+        if (same) {
+            point_image(img, pt, variant);
+            const int len = payload_from_point(format, img, mine);
+            same = len != 0 && memcmp(mine, payload, (size_t)len) == 0;
+        }
+        if (!same) {
+            if (bk.dropped) bk.dropped->fetch_add(1, std::memory_order_relaxed);
+            return false;
+        }
+        scalar_to_be(k, g.key);
+        memcpy(g.address, addr.c_str(), addr.size() + 1);
+        return true;
+    }
     if (variant) {
         Scalar kv;
         scalar_variant(kv, k, variant);
@@ -119,9 +146,11 @@ inline bool make_match(const vgen_filter &flt, uint32_t format, const BatchKeys 
 }
 
 // GeneratedAddress (src/address.rs:63-72) of a match: address, WIF (src/gpu.rs:1080-1088), hex, format, key.
-inline void render_match(uint32_t format, const LiteMatch &m, vgen_generated &g) {
+// `partial` (split-key scans): the key is a partial key - hex = wif = "0x" + its lowercase hex, the CREATE2 convention, never a WIF: a
+// partial key must not look importable.
+inline void render_match(uint32_t format, const LiteMatch &m, vgen_generated &g, bool partial = false) {
     memset(&g, 0, sizeof g);
-    const std::string wif = key_to_wif(format, m.key), hex = hex_lower(m.key, 32);
+    const std::string hex = (partial ? "0x" : "") + hex_lower(m.key, 32), wif = partial ? hex : key_to_wif(format, m.key);
     strncpy(g.address, m.address, sizeof g.address - 1);
     strncpy(g.wif, wif.c_str(), sizeof g.wif - 1);
     strncpy(g.hex, hex.c_str(), sizeof g.hex - 1);

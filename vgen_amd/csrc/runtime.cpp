@@ -233,6 +233,18 @@ static int create2_dispatch(vgen_ctx *c, uint32_t frame, uint64_t first_counter)
 static int create3_set(vgen_ctx *c, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
                        const uint8_t *guard, int guard_len);
 
+// The base point of split-key dispatches (vgen_set_base_point; cabi.cpp has parsed the key and checked that nothing is in flight).
+// Host-side state only: the walk's uniform points carry it from the next dispatch on (host_seq_points starts afresh when the base it
+// is given differs from the cached points'; dropped here too, so that no point of another base outlives the call) and the
+// arbitrary-scalar kernels get it by value.
+static int base_set(vgen_ctx *c, const ge *pt) {
+    c->have_base = pt != nullptr;
+    if (pt) c->base_pt = *pt;
+    c->base_cache.valid = false;
+    c->base_cache.ahead_n = c->base_cache.ahead_pos = 0;
+    return VGEN_OK;
+}
+
 int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
     // ABI 4's parameter block, or ABI 3's 28 bytes (no table_bits, no budget: both automatic)
     constexpr uint32_t PARAMS_ABI3 = 28;
@@ -420,6 +432,7 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
     lap("memset + table kernel + sync");
     if (int rc = rt_set_match_cap(c, c->match_cap)) return bail(rc, c->err);
     lap("match rings (device + pinned)");
+    c->base_set = base_set;
     *out = c;
     return VGEN_OK;
 }
@@ -1272,6 +1285,13 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
         for (int i = 0; i < 8; i++) a.base[i] = base->w[i];
     a.filter = c->d_filter;
     a.n = n;
+    if (c->have_base) {   // split-key dispatch: keys_fwd_base_kernel adds the base to every lane's k*G
+        a.has_base = 1;
+        for (int i = 0; i < 9; i++) {
+            a.base_pt.x[i] = c->base_pt.x.n[i];
+            a.base_pt.y[i] = c->base_pt.y.n[i];
+        }
+    }
     a.fmt = (uint32_t)vgf_string_format((int)c->format);   // what the on-device matcher spells the payload as
     const uint32_t max_groups = (c->batch + KEYS_WG - 1) / KEYS_WG;
     a.groups = (n + KEYS_WG - 1) / KEYS_WG;
@@ -1348,7 +1368,14 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
     Scalar kb;
     scalar_add_u64(kb, k0, (uint64_t)c->batch / 2 - S / 2);
     ge aff[32];
-    if (!host_seq_points(c->base_cache, kb, S, aff)) return c->fail(VGEN_E_RANGE, "base point at infinity");
+    // Split-key walks: Q_j + P in Q_j's place moves the whole walk onto the requester's point; the kernels add and subtract the
+    // offsets R_u as ever.  ("No exceptional cases" is then a statement about the effective scalar s + k, which the host does not
+    // know: see make_match's re-derivation.)  A uniform point at infinity - k0 + N/2 - S/2 + j = -s - sends the batch through the
+    // complete per-key kernels, like the batches at the top of the range.
+    if (!host_seq_points(c->base_cache, kb, S, aff, c->have_base ? &c->base_pt : nullptr)) {
+        if (c->have_base) return enqueue_keys(c, f, nullptr, &k0, c->batch);
+        return c->fail(VGEN_E_RANGE, "base point at infinity");
+    }
 
     SeqArgs a;
     memset(&a, 0, sizeof a);

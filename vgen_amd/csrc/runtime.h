@@ -94,6 +94,13 @@ struct vgen_ctx {
     uint32_t create3_w[26] = {0};
     int (*create3_set)(vgen_ctx *, const uint8_t factory[20], const uint8_t proxy_init_code_hash[32], const uint8_t salt_prefix[24],
                        const uint8_t *guard, int guard_len) = nullptr;
+    // Split-key search (vgen_set_base_point): the requester's public key P.  With it every dispatch tests P + k*G instead of k*G and
+    // the scan loop reports partial keys.  Host-side state, installed through base_set, which a runtime that honours a base sets
+    // (nullptr elsewhere: vgen_set_base_point is then VGEN_E_UNSUPPORTED).  pt = nullptr clears.
+    bool have_base = false;
+    vg::ge base_pt{};
+    int (*base_set)(vgen_ctx *, const vg::ge *pt) = nullptr;
+    std::atomic<uint64_t> split_dropped{0};   // scan candidates the host re-derivation refused (scan_match.h: make_match)
     // DEVF_SCORE: the terms of the installed score filter (set by rt_set_filter, the first threshold replaced by vgen_set_score_min;
     // n = 0 for every other filter and in dump mode).  Copied by value into each dispatch's kernel arguments.
     vg::ScoreTerms score{};

@@ -377,6 +377,12 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
     auto stopped = [&]() { return job.stop && __atomic_load_n(const_cast<const int32_t *>(job.stop), __ATOMIC_RELAXED) != 0; };
     auto in_range = [&]() { return !exhausted && (!end || scalar_cmp(current, *end) <= 0); };
     auto can_dispatch = [&]() { return in_range() && (!cfg->max_batches || dispatched + taken_over < cfg->max_batches); };
+    // a batch dispatched under a base point: its candidates are re-derived from that point (make_match) and yield partial keys
+    auto mark_split = [&](BatchKeys &bk) {
+        if (!ctx->have_base) return;
+        bk.base = &ctx->base_pt;
+        bk.dropped = &ctx->split_dropped;
+    };
     auto dispatch = [&](uint32_t frame) -> int {
         if (random_keys) {
             // every shard owns a stream of its own and walks its candidates in order (the oracle's worker thread, oracle/vo_scan.c)
@@ -396,6 +402,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
             pend[frame].seed = rnd_seed;
             pend[frame].stream = shard;
             pend[frame].first_index = first;
+            mark_split(pend[frame]);
             dispatched++;
             return VGEN_OK;
         }
@@ -406,6 +413,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
         pend[frame] = BatchKeys{};
         pend[frame].batch_no = skipped + dispatched;
         pend[frame].start = current;
+        mark_split(pend[frame]);
         dispatched++;
         Scalar nx;
         if (scalar_add_u64(nx, current, stride) || !scalar_is_valid(nx)) exhausted = true;   // key space exhausted
@@ -640,7 +648,8 @@ int open_checkpoint(vgen_ctx *ctx, Checkpoint &ck, const char *pattern, vgen_sca
 
 // Hands the matches to the caller as GeneratedAddress records: this is where WIF and hex are rendered — for the matches that
 // survived `count`, straight into the result array, on several threads when there are thousands.
-int finish_result(vgen_ctx *ctx, uint32_t format, const MatchList &matches, uint64_t ops, double secs, vgen_scan_result *out) {
+// (`partial`: a split-key scan's keys are partial keys and are rendered as such, render_match)
+int finish_result(vgen_ctx *ctx, uint32_t format, const MatchList &matches, uint64_t ops, double secs, vgen_scan_result *out, bool partial = false) {
     out->n_matches = matches.size();
     out->operations = ops;
     if (!matches.empty()) {
@@ -656,7 +665,7 @@ int finish_result(vgen_ctx *ctx, uint32_t format, const MatchList &matches, uint
             size_t base = 0;
             for (auto &b : blocks) {
                 const size_t from = std::max(lo, base), to = std::min(hi, base + b.size());
-                for (size_t i = from; i < to; i++) render_match(format, b[i - base], out->matches[i]);
+                for (size_t i = from; i < to; i++) render_match(format, b[i - base], out->matches[i], partial);
                 base += b.size();
                 if (base >= hi) break;
             }
@@ -705,6 +714,25 @@ static int check_best(vgen_ctx *ctx, const vgen_scan_config &c, const vgen_filte
     return VGEN_OK;
 }
 
+// Split-key scans (contexts with a base point, vgen_set_base_point): one base for all contexts of the scan, and none of what stores
+// keys and re-derives addresses from them - a partial key alone derives nothing.  *split receives whether the scan is one.
+static int check_split(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_scan_config &c, bool list, bool *split) {
+    bool any = false;
+    for (uint32_t i = 0; i < n_ctx; i++) any = any || ctxs[i]->have_base;
+    *split = any;
+    if (!any) return VGEN_OK;
+    vgen_ctx *c0 = ctxs[0];
+    for (uint32_t i = 0; i < n_ctx; i++)
+        if (!ctxs[i]->have_base || !fe_equal_canonical(ctxs[i]->base_pt.x, c0->base_pt.x) || !fe_equal_canonical(ctxs[i]->base_pt.y, c0->base_pt.y))
+            return c0->fail(VGEN_E_INVALID, "split-key scan: all contexts must have the same base point (vgen_set_base_point)");
+    if (list) return c0->fail(VGEN_E_UNSUPPORTED, "vgen_scan_list is not supported on contexts with a base point (split-key): lists work per dispatch there");
+    if (c.checkpoint_path)
+        return c0->fail(VGEN_E_UNSUPPORTED, "checkpoint_path is not supported on contexts with a base point (split-key): a checkpoint stores keys and "
+                                            "re-derives addresses from them, and a partial key derives nothing");
+    if (c.has_end) return c0->fail(VGEN_E_UNSUPPORTED, "key ranges (has_end) are not supported on contexts with a base point (split-key)");
+    return VGEN_OK;
+}
+
 extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_config *cfg_in, vgen_progress_cb cb,
                          void *user, const volatile int32_t *stop, vgen_scan_result *out) {
     vgen_scan_config c;   // (a checkpoint may give it the file's base key)
@@ -721,6 +749,8 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
     // all their matches), and nothing is dispatched when the file says the scan is complete or already holds `count` matches.
     // While the shard runs, its matches stay the first `count` of the checkpoint's record: they serve every way out.
     if (int rc = check_best(ctx, c, flt)) return rc;
+    bool split = false;
+    if (int rc = check_split(&ctx, 1, c, false, &split)) return rc;
     std::unique_ptr<Checkpoint> ck;
     RndSeed rnd_seed{};
     ResultSink sink(c.count);
@@ -758,7 +788,7 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
     // src/lib.rs:727-746,1185-1198) keeps those matches
     const std::string why = ctx->err;
     if (sink.best) sink.matches.take(std::vector<LiteMatch>(bl.accepted), bl.accepted.size());
-    const int frc = finish_result(ctx, c.format, sink.matches, job.operations, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
+    const int frc = finish_result(ctx, c.format, sink.matches, job.operations, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out, split);
     if (rc != VGEN_OK) {
         out->failed_shards = 1;
         ctx->err = why;
@@ -776,6 +806,8 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
 static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &flt, const char *pattern, const vgen_scan_config *cfg,
                           vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out, ListLedger *ll) {
     if (int rc = check_best(ctxs[0], *cfg, flt)) return rc;
+    bool split = false;
+    if (int rc = check_split(ctxs, n_ctx, *cfg, ll != nullptr, &split)) return rc;
     BestLedger best_ledger;
     BestLedger *bl = (cfg->flags & VGEN_SCAN_BEST) ? &best_ledger : nullptr;
     const auto t0 = std::chrono::steady_clock::now();
@@ -947,7 +979,7 @@ static int scan_multi_run(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter &fl
     MatchList result;
     result.take(std::move(all), (size_t)std::min<uint64_t>(all.size(), cfg->count));
     const std::string why = first_err != VGEN_OK ? ctxs[first_err_ctx]->err : std::string();
-    const int frc = finish_result(ctxs[0], cfg->format, result, total, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out);
+    const int frc = finish_result(ctxs[0], cfg->format, result, total, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), out, split);
     if (first_err != VGEN_OK && !absorbed) {
         out->complete = 0;
         ctxs[first_err_ctx]->err = why;
