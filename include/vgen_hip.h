@@ -75,6 +75,33 @@ typedef enum vgen_format {
  * VGEN_FLAG_ENDO).
  * No score patterns. */
 #define VGEN_FMT_NOSTR 10u
+/* And one on another curve: VGEN_FMT_SOLANA, 12 (not a format of the reference; 11 stays unassigned like 8 and 9).  A Solana address
+ * is an Ed25519 public key, and what a wallet imports is the SEED it was made from: the KEY of this format is the 32-byte seed (any 32
+ * bytes are one), the scalar is a = clamp(SHA-512(seed)[0..31]) (RFC 8032 5.1.5: little-endian, bits 0-2 and 255 cleared, bit 254
+ * set) - so seed + 1 is no neighbour of seed and NOTHING CAN BE WALKED: every candidate costs one SHA-512 block and one fixed-base
+ * multiplication.  Payload: the 32 bytes of A = a*B as RFC 8032 encodes them (y little-endian, fully reduced, the sign of x in bit
+ * 255), in memory order; never all zero (y = 0 is a point of order 4).  Address string: Base58 (Bitcoin alphabet, no version, no
+ * checksum) of those 32 bytes read as one big-endian number N, a leading '1' per leading zero byte: 32 to 44 characters, 44 for
+ * 94.2 % of keys and 43 for 5.7 %.  The first character is far from uniform ('2' .. 'H' take about 1/17 each, 'K' .. 'z' about
+ * 1/1000 each, and an address shorter than 43 characters starts with '1').
+ * Entry points: vgen_create (VGEN_FLAG_ENDO: VGEN_E_UNSUPPORTED; no secp256k1 scratch or generator table is allocated - the 0.9 MB
+ * Ed25519 table is shared per device and counted in vgen_memory_info.table_bytes), vgen_dispatch_keys (keys_be holds SEEDS; slots >=
+ * n are zero), vgen_dispatch_random / vgen_dispatch_random_seed (lane i tests the seed vgen_solana_seed(seed, stream, first_index +
+ * i): the stream's digest itself, every draw a key), vgen_wait, vgen_read_dump / vgen_dump_view (32 B per slot), vgen_set_filter,
+ * vgen_set_match_cap, the frame timers, vgen_address_from_payload, vgen_derive (address; wif = the seed's 64 lowercase hex digits -
+ * wif[72] cannot hold the keypair string, see vgen_solana_keypair_base58), vgen_key_to_wif (the same hex), the pattern front end
+ * (Base58; difficulty 58^k or 34^k, no constant prefix - mind the first-character caveat above) and vgen_scan / vgen_scan_multi,
+ * which ALWAYS run the random-key loop on such a context (VGEN_SCAN_RANDOM_KEYS is implied): batch b of shard s tests candidates
+ * b * batch_size .. of stream s; seed 0 = 24 bytes of OS entropy, and the warning at vgen_dispatch_random_seed applies word for
+ * word - a nonzero 64-bit seed makes the keys guessable; has_start, has_end and checkpoint_path are VGEN_E_UNSUPPORTED.  A result
+ * carries key = the seed, hex = wif = its hex, format = 12; each is re-derived on the host before it is reported.
+ * VGEN_E_UNSUPPORTED with a message: vgen_dispatch (no walk), vgen_set_base_point / vgen_split_derive / vgen_split_combine,
+ * vgen_filter_compile_list, score specifications, vgen_scan_list.
+ * Device filter kinds (vgen_filter_device_kind): 1 = ranges of N (prefixes: at most two ranges per literal prefix, one per address
+ * length; with classes or case-insensitivity the longest shortened prefix whose ranges fit 64 tests), 7 = a test of N modulo 58^k,
+ * k <= 5 (the last characters), alone or with ranges (a pattern anchored at both ends), 3 = match-all, 0 = neither end is usable:
+ * every payload goes to the host (correct and slow).  The device test is a superset; the host confirms with the exact automaton. */
+#define VGEN_FMT_SOLANA 12u
 
 /* Parameters of vgen_create; replaces the arguments of GpuRunner::new(batch_size, backend)
  * (src/gpu.rs:138) plus the buffer sizing it derives from them (src/gpu.rs:391-500). */
@@ -636,6 +663,19 @@ int vgen_scan_create3(vgen_ctx **ctxs, uint32_t n_ctx, const char *pattern, cons
                       const uint8_t salt_prefix[24], const uint8_t *guard, int32_t guard_len, uint64_t first_counter,
                       const vgen_scan_config *cfg, vgen_progress_cb cb, void *user, const volatile int32_t *stop, vgen_scan_result *out);
 void vgen_scan_result_free(vgen_scan_result *r);
+
+/* ---- Solana (VGEN_FMT_SOLANA) ------------------------------------------------------------------------------------------------ */
+/* Candidate `index` of stream `stream` under `seed`: the 32 bytes vgen_dispatch_random*'s lane (index - first_index) tests on a
+ * format-12 context (the bytes vgen_random_key_seed returns, without its range test: every draw is a key).  Never fails.  The u64
+ * seeds of the ABI stand for u64le(seed) || sixteen zero bytes, as elsewhere. */
+int vgen_solana_seed(const uint8_t seed[24], uint32_t stream, uint64_t index, uint8_t out[32]);
+/* RFC 8032 5.1.5: the public key (= the address's 32 bytes) of a seed. */
+int vgen_solana_public_key(const uint8_t seed[32], uint8_t pub[32]);
+/* Base58 of seed || public key, the string wallets import as a private key; cap >= 89.  Returns the length. */
+int vgen_solana_keypair_base58(const uint8_t seed[32], char *out, size_t cap);
+/* Strict: VGEN_E_INVALID for a character outside the Base58 alphabet or a value that is not exactly 32 bytes.  Curve membership
+ * is not tested. */
+int vgen_solana_decode(const char *address, uint8_t pub[32]);
 
 #ifdef __cplusplus
 }

@@ -59,6 +59,9 @@ class AddressFormat(enum.IntEnum):
 # VGEN_FMT_NOSTR: the Nostr public key npub1... (NIP-19), the BIP-340 x-only key itself (not in the reference).  A plain number outside
 # the enumeration, as in the header (8 and 9 stay unassigned); every function that takes a format takes it.
 FORMAT_NOSTR = 10
+# VGEN_FMT_SOLANA: a Solana address, the Ed25519 public key of a 32-byte seed in Base58 (not in the reference).  The key of this format
+# is the SEED; 11 stays unassigned.  Scans of such a runner always draw independent seeds (ScanConfig.random_keys is implied).
+FORMAT_SOLANA = 12
 
 
 def _fmt(v):
@@ -161,6 +164,10 @@ _L.vgen_contract_address.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_
 _L.vgen_keccak256.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p]
 _L.vgen_nostr_encode.argtypes = [ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
 _L.vgen_nostr_decode.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p]
+_L.vgen_solana_seed.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_char_p]
+_L.vgen_solana_public_key.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+_L.vgen_solana_keypair_base58.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+_L.vgen_solana_decode.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
 _L.vgen_create2_address.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
 _L.vgen_create2_salt.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
 _L.vgen_set_create2.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
@@ -322,6 +329,51 @@ def npub_from_key(key) -> str:
 def nsec_from_key(key) -> str:
     """The NIP-19 rendering nsec1... of a secret key, as it is (no parity normalisation)."""
     return key_to_wif(FORMAT_NOSTR, key)
+
+
+def _seed32(seed) -> bytes:
+    seed = bytes.fromhex(seed) if isinstance(seed, str) else bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("an Ed25519 seed is 32 bytes")
+    return seed
+
+
+def solana_seed(seed, stream: int, index: int) -> bytes:
+    """vgen_solana_seed: the 32-byte Ed25519 seed a Solana runner's dispatch_random tests as candidate `index` of stream `stream`.
+    seed: an integer < 2^64 (standing for its 8 little-endian bytes and sixteen zero bytes) or the 24 seed bytes."""
+    if not isinstance(seed, (bytes, bytearray)):
+        seed = int(seed).to_bytes(8, "little") + bytes(16)
+    assert len(seed) == 24
+    out = ctypes.create_string_buffer(32)
+    _check(_L.vgen_solana_seed(bytes(seed), stream, index, out))
+    return out.raw
+
+
+def solana_public_key(seed) -> bytes:
+    """vgen_solana_public_key: the Ed25519 public key (RFC 8032) of a 32-byte seed - the 32 bytes of the address."""
+    out = ctypes.create_string_buffer(32)
+    _check(_L.vgen_solana_public_key(_seed32(seed), out))
+    return out.raw
+
+
+def solana_address(seed) -> str:
+    """The Solana address of a seed: Base58 of its public key."""
+    return address_from_payload(FORMAT_SOLANA, solana_public_key(seed))
+
+
+def solana_keypair_base58(seed) -> str:
+    """vgen_solana_keypair_base58: Base58 of seed || public key, the string wallets import as a private key."""
+    out = ctypes.create_string_buffer(96)
+    _check(_L.vgen_solana_keypair_base58(_seed32(seed), out, 96))
+    return out.value.decode()
+
+
+def solana_decode(address: str) -> Optional[bytes]:
+    """vgen_solana_decode (strict) -> the 32 bytes, or None when `address` is not Base58 of exactly 32 bytes."""
+    out = ctypes.create_string_buffer(32)
+    if _L.vgen_solana_decode(address.encode(), out) != 0:
+        return None
+    return out.raw
 
 
 def contract_address(deployer, nonce=0) -> bytes:
@@ -667,7 +719,7 @@ class GpuRunner:
         b, f, m = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         _L.vgen_get_info(h, ctypes.byref(b), ctypes.byref(f), ctypes.byref(m))
         self.batch_size, self.frames, self.match_cap, self.format = b.value, f.value, m.value, _fmt(fmt)
-        self.payload_bytes = 32 if int(self.format) in (int(AddressFormat.P2tr), FORMAT_NOSTR) else 20
+        self.payload_bytes = 32 if int(self.format) in (int(AddressFormat.P2tr), FORMAT_NOSTR, FORMAT_SOLANA) else 20
         self._pattern = None
 
     def topology(self) -> dict:

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/vgen_hip.h"
+#include "host/ed_host.h"
 #include "host/encode.h"
 #include "host/filter.h"
 #include "host/pattern_info.h"
@@ -109,6 +110,10 @@ int vgen_filter_matches(const vgen_filter *f, const char *address) {
 
 int vgen_filter_compile_list(const char *patterns, int case_insensitive, uint32_t format, vgen_filter **out) {
     if (!patterns || !out) return VGEN_E_INVALID;
+    if (format == vg::VGF_SOLANA) {
+        g_last_error = "pattern lists are not provided for the solana format (12): a list's table holds intervals of 64 payload bits, Base58 of 32 bytes needs all 256";
+        return VGEN_E_UNSUPPORTED;
+    }
     vgen_filter *f = new vgen_filter();
     std::string err;
     if (!vg::filter_compile_list(patterns, case_insensitive != 0, format, *f, err)) {
@@ -324,6 +329,7 @@ int vgen_address_from_payload(uint32_t format, const uint8_t *payload, char *out
 
 int vgen_key_to_wif(uint32_t format, const uint8_t key_be[32], char *out, size_t cap) {
     if (!key_be) return VGEN_E_INVALID;
+    if (format == vg::VGF_SOLANA) return copy_out(vg::key_to_wif(format, key_be), out, cap);   // a seed: any 32 bytes
     vg::Scalar k;
     vg::scalar_from_be(k, key_be);
     if (!vg::scalar_is_valid(k)) return VGEN_E_RANGE;
@@ -476,6 +482,8 @@ int vgen_set_base_point(vgen_ctx *ctx, const uint8_t *pub, size_t len) {
     if (!ctx) return VGEN_E_INVALID;
     if (ctx->format == vg::VGF_ETHEREUM_CREATE2)
         return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: an ethereum-create2 context tests salts - there is no key to split");
+    if (ctx->format == vg::VGF_SOLANA)
+        return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: a solana key is a seed whose scalar is its hash - partial keys cannot be added");
     if (!ctx->base_set) return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: this runtime does not serve split-key dispatches");
     const bool clear = !pub && len == 0;
     vg::ge pt;
@@ -502,7 +510,7 @@ int vgen_split_dropped(const vgen_ctx *ctx, uint64_t *n) {
 
 int vgen_split_derive(uint32_t format, const uint8_t *pub, size_t len, const uint8_t partial_be[32], uint32_t variant, char *address, size_t cap) {
     if (!pub || !partial_be || !address) return VGEN_E_INVALID;
-    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2) return VGEN_E_UNSUPPORTED;
+    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2 || format == vg::VGF_SOLANA) return VGEN_E_UNSUPPORTED;
     vg::ge base, pt, img;
     if (variant >= vg::vgf_endo_images((int)format) || !vg::point_from_sec1(pub, len, base)) return VGEN_E_INVALID;
     vg::Scalar k;
@@ -518,7 +526,7 @@ int vgen_split_derive(uint32_t format, const uint8_t *pub, size_t len, const uin
 int vgen_split_combine(uint32_t format, const uint8_t secret_be[32], const uint8_t partial_be[32], const char *address, uint8_t final_be[32],
                        uint32_t *variant) {
     if (!secret_be || !partial_be || !address || !final_be) return VGEN_E_INVALID;
-    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2) return VGEN_E_UNSUPPORTED;
+    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2 || format == vg::VGF_SOLANA) return VGEN_E_UNSUPPORTED;
     vg::Scalar s, k, sum;
     vg::scalar_from_be(s, secret_be);
     vg::scalar_from_be(k, partial_be);
@@ -555,6 +563,34 @@ int vgen_split_combine(uint32_t format, const uint8_t secret_be[32], const uint8
         }
     }
     return VGEN_E_INVALID;
+}
+
+// ---- Solana ----
+
+int vgen_solana_seed(const uint8_t seed[24], uint32_t stream, uint64_t index, uint8_t out[32]) {
+    if (!seed || !out) return VGEN_E_INVALID;
+    // the digest core/rnd.h draws, in its natural byte order: what vgen_random_key_seed returns, without its range test
+    vg::u32 k[8];
+    vg::rnd_scalar(vg::rnd_seed_from_bytes(seed), stream, (vg::u32)index, (vg::u32)(index >> 32), k);
+    for (int i = 0; i < 8; i++)
+        for (int b = 0; b < 4; b++) out[4 * i + b] = (uint8_t)(k[7 - i] >> (8 * (3 - b)));
+    return VGEN_OK;
+}
+
+int vgen_solana_public_key(const uint8_t seed[32], uint8_t pub[32]) {
+    if (!seed || !pub) return VGEN_E_INVALID;
+    vg::ed_public_key(seed, pub);
+    return VGEN_OK;
+}
+
+int vgen_solana_keypair_base58(const uint8_t seed[32], char *out, size_t cap) {
+    if (!seed || !out || cap < 89) return VGEN_E_INVALID;
+    return copy_out(vg::solana_keypair_base58(seed), out, cap);
+}
+
+int vgen_solana_decode(const char *address, uint8_t pub[32]) {
+    if (!address || !pub) return VGEN_E_INVALID;
+    return vg::solana_decode(address, pub) ? VGEN_OK : VGEN_E_INVALID;
 }
 
 }  // extern "C"

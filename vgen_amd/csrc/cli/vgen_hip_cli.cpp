@@ -8,11 +8,13 @@
 // only), --devices (batch-striped multi-GPU scan), --frames, --checkpoint (resumable scans).
 #include <ctype.h>
 #include <errno.h>
+#include <fcntl.h>
 #include <signal.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
 
@@ -54,6 +56,7 @@ struct Opts {
     bool has_proxy_hash = false, has_salt_guard = false, salt_guard_hash = false;
     // split-key search: --base-pubkey (generate), and the requester's `combine`
     std::string base_pubkey, secret_file, partial;
+    std::string keypair_dir;                  // -f solana: one <address>.json per result, the 64-number array solana-keygen reads
     bool has_base = false;
     bool create3() const { return format == "ethereum-create3"; }
     bool any_create3_option() const { return has_proxy_hash || has_salt_guard || salt_guard_hash; }
@@ -76,7 +79,8 @@ int format_id(const std::string &f) {
     if (f == "ethereum-create3") return VGEN_FMT_ETHEREUM_CREATE2;   // no format of its own: a CREATE3 job on a format-7 context (Opts::create3)
     if (f == "p2pkh-uncompressed") return VGEN_FMT_P2PKH_UNCOMPRESSED;
     if (f == "nostr") return VGEN_FMT_NOSTR;
-    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2, ethereum-create3, nostr)");
+    if (f == "solana") return VGEN_FMT_SOLANA;
+    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2, ethereum-create3, nostr, solana)");
 }
 
 const char *format_display(int id) {   // Display for AddressFormat, src/address.rs:48-58
@@ -89,6 +93,7 @@ const char *format_display(int id) {   // Display for AddressFormat, src/address
     case VGEN_FMT_ETHEREUM_CONTRACT: return "Ethereum contract (nonce 0)";   // (no comma: the csv writer keeps eight plain columns)
     case VGEN_FMT_ETHEREUM_CREATE2: return "Ethereum contract (CREATE2)";
     case VGEN_FMT_NOSTR: return "Nostr (npub)";
+    case VGEN_FMT_SOLANA: return "Solana";
     default: return "Ethereum";
     }
 }
@@ -207,7 +212,8 @@ void usage() {
             "  FORMAT: p2pkh (default), p2wpkh, p2sh-p2wpkh, p2tr, p2pkh-uncompressed, ethereum, ethereum-contract (the address of the\n"
             "          contract the key's account creates with its FIRST transaction, nonce 0; results carry that account as `deployer`),\n"
             "          nostr (the Nostr public key npub1... of NIP-19: Bech32 of the BIP-340 x-only key; results carry the nsec1... secret key\n"
-            "          as `wif` and the key's 32 bytes as `public_key_hex`; unseeded searches test three keys per curve point)\n"
+            "          as `wif` and the key's 32 bytes as `public_key_hex`; unseeded searches test three keys per curve point),\n"
+            "          solana (see below)\n"
             "  vgen-hip generate -p PATTERN [-f FORMAT] [-i] [-c COUNT] [-o text|json|jsonl|csv|minimal] [--file PATH]\n"
             "                    [--gpu-batch-size N] [--repeat N] [-q] [--seed S] [--devices 0,1,..|all] [--frames F]\n"
             "                    [--frames F]          (dispatches in flight, default 12; several searches on ONE device share it\n"
@@ -245,6 +251,11 @@ void usage() {
             "  vgen-hip combine --secret-file PATH --partial HEX --address ADDR [-f FORMAT]   (the requester's side: PATH holds the secret, 32\n"
             "                    bytes or 64 hex digits - never on the command line; prints the final key (secret + partial) mod n, under the\n"
             "                    image that gives ADDR, as the format prints keys; fails if no image of the sum has that address)\n"
+            "  vgen-hip generate -f solana -p PATTERN [-i] [-c COUNT] [-o ..] [--devices ..] [--seed S] [--keypair-dir DIR]   (Solana addresses:\n"
+            "                    Base58 of an Ed25519 public key.  The key is the 32-byte SEED; every candidate is an independent draw (--random-keys\n"
+            "                    and --no-endo are accepted and change nothing).  Results carry the seed in hex and the keypair string wallets\n"
+            "                    import; --keypair-dir writes DIR/<address>.json, the 64-number array solana-keygen reads, mode 0600.  --seed makes\n"
+            "                    the keys guessable.  estimate takes the format; range, --checkpoint, --patterns-file and --base-pubkey do not)\n"
             "  vgen-hip generate --patterns-file FILE [--per-pattern N] ...   (instead of -p: one start-anchored prefix per line,\n"
             "                    one scan; N results per pattern (default 1, 0 = unbounded), -c caps the total (default: none);\n"
             "                    each result's pattern field is the lowest-index line it satisfies.  range takes it too)\n"
@@ -269,7 +280,7 @@ Opts parse(int argc, char **argv) {
                                                   "--seed", "--devices", "--frames", "--checkpoint", "--range", "--puzzle", "--key", "--address",
                                                   "--prefix-length", "--provider-table", "--threads", "--backend", "--cpu-batch-size", "--table-bits-max",
                                                   "--mem-budget-gib", "--patterns-file", "--per-pattern", "--deployer", "--init-code-hash", "--init-code-file",
-                                                  "--salt-prefix", "--salt-start", "--proxy-init-code-hash", "--salt-guard", "--base-pubkey", "--secret-file", "--partial"};
+                                                  "--salt-prefix", "--salt-start", "--proxy-init-code-hash", "--salt-guard", "--base-pubkey", "--secret-file", "--partial", "--keypair-dir"};
     static const char short_with_value[] = "pfcorkaltT";
     std::vector<std::string> args;
     bool next_is_value = false;
@@ -351,6 +362,7 @@ Opts parse(int argc, char **argv) {
         else if (a == "--base-pubkey") { o.base_pubkey = val(); o.has_base = true; }
         else if (a == "--secret-file") o.secret_file = val();
         else if (a == "--partial") o.partial = val();
+        else if (a == "--keypair-dir") o.keypair_dir = val();
         else if (a == "-t" || a == "--threads" || a == "--backend" || a == "--cpu-batch-size") (void)val();   // accepted, not applicable
         else if (a == "-h" || a == "--help") { usage(); exit(0); }
         else die("unexpected argument '" + a + "'");
@@ -637,6 +649,22 @@ vgen_filter *load_pattern_list(const Opts &o, int fmt) {
 }
 
 // The text of the lowest-index pattern of `list` that `address` satisfies (a result's `pattern` field).
+// -f solana --keypair-dir: DIR/<address>.json holds the 64 bytes seed || public key as a JSON array of numbers, the file
+// `solana-keygen` and `solana config set --keypair` read; created with mode 0600 (a private key).
+void write_keypair_file(const std::string &dir, const vgen_generated &g) {
+    uint8_t kp[64];
+    memcpy(kp, g.key, 32);
+    if (vgen_solana_public_key(g.key, kp + 32) != VGEN_OK) die("a result of a solana search has no public key");
+    const std::string path = dir + "/" + g.address + ".json";
+    const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0600);
+    if (fd < 0 || fchmod(fd, 0600) != 0) die("cannot write keypair file '" + path + "'");
+    std::string text = "[";
+    for (int i = 0; i < 64; i++) text += (i ? "," : "") + std::to_string(kp[i]);
+    text += "]\n";
+    const bool ok = write(fd, text.data(), text.size()) == (ssize_t)text.size();
+    if (close(fd) != 0 || !ok) die("cannot write keypair file '" + path + "'");
+}
+
 std::string list_pattern_of(const vgen_filter *list, const char *address) {
     uint32_t idx = 0, n = 0;
     if (vgen_filter_which(list, address, &idx, 1, &n) != VGEN_OK || n == 0) return std::string();
@@ -655,6 +683,13 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         die("'--deployer', '--init-code-hash', '--init-code-file', '--salt-prefix' and '--salt-start' belong to '-f ethereum-create2'");
     if (!create3 && o.any_create3_option())
         die("'--proxy-init-code-hash', '--salt-guard' and '--salt-guard-hash' belong to '-f ethereum-create3'");
+    const bool solana = fmt == VGEN_FMT_SOLANA;
+    if (solana) {   // a seed has no neighbour: nothing walks, nothing resumes, nothing splits
+        if (has_range) die("'-f solana' cannot be used with 'range': a solana key is a seed whose scalar is its hash - there is no key range");
+        if (!o.checkpoint.empty()) die("the argument '--checkpoint' cannot be used with '-f solana': checkpoints are not provided for this format");
+        if (list) die("the argument '--patterns-file' cannot be used with '-f solana': pattern lists are not provided for this format");
+        if (o.has_base) die("the argument '--base-pubkey' cannot be used with '-f solana': a seed cannot be split");
+    } else if (!o.keypair_dir.empty()) die("the argument '--keypair-dir' belongs to '-f solana'");
     Create2Job job;
     Create3Job job3;
     if (create3) job3 = create3_job(o, has_range, list != nullptr);
@@ -696,7 +731,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         // a vanity search proper — random base, no range, no seed, no checkpoint — may test any keys it likes:
         // six images per curve point (VGEN_FLAG_ENDO, +30 % keys per second); everything else walks k0 + i
         // (--random-keys: six keys per draw; seeds name candidate streams there, so they do not rule it out)
-        if (!o.no_endo && fmt != 3 && !create2 && (o.random_keys || (!has_range && !o.seed && o.checkpoint.empty()))) p.flags |= VGEN_FLAG_ENDO;
+        if (!o.no_endo && fmt != 3 && !create2 && !solana && (o.random_keys || (!has_range && !o.seed && o.checkpoint.empty()))) p.flags |= VGEN_FLAG_ENDO;
         vgen_ctx *c = nullptr;
         if (vgen_create(&p, &c) != VGEN_OK) die(std::string("GPU initialization failed: ") + vgen_last_error(nullptr));
         if (o.has_base && vgen_set_base_point(c, base_pub, (size_t)base_len) != VGEN_OK) die(vgen_last_error(c));
@@ -827,8 +862,25 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
                 c3_guarded = hex0x(gs, 32);
             }
         }
+        // solana: the key is the seed; the keypair string is what wallets import, the address's 32 bytes are the public key
+        std::string keypair;
+        if (solana) {
+            char kp[96];
+            if (vgen_solana_keypair_base58(g.key, kp, sizeof kp) < 0) die("a result of a solana search has no keypair string");
+            keypair = kp;
+            if (!o.keypair_dir.empty()) write_keypair_file(o.keypair_dir, g);
+        }
         // nostr: the address is the Bech32 of the x-only public key; its 32 bytes in hex beside it
         std::string pub_hex;
+        if (solana) {
+            uint8_t pub[32];
+            if (vgen_solana_decode(g.address, pub) != VGEN_OK) die("a result of a solana search is no address");
+            static const char HX[] = "0123456789abcdef";
+            for (int i = 0; i < 32; i++) {
+                pub_hex.push_back(HX[pub[i] >> 4]);
+                pub_hex.push_back(HX[pub[i] & 15]);
+            }
+        }
         if (fmt == VGEN_FMT_NOSTR) {
             uint32_t kind = 0;
             uint8_t pub[32];
@@ -844,6 +896,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         if (o.output == "text") {
             fprintf(w, "=== Match %zu of %zu ===\n", idx + 1, all.size());
             if (create2) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSalt    : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex);
+            else if (solana) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSeed    : %s\nKeypair : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex, keypair.c_str());
             else if (o.has_base) {
                 // a partial key: no key to anything without the secret behind the base public key (vgen-hip combine)
                 fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nPartial key : %s\nBase pubkey : %s\nVariant : %d\n", pattern.c_str(), fmt_name.c_str(),
@@ -876,7 +929,8 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             if (score_flt) fprintf(w, "%s\"score\":%s%u,", nl, sp, score);
             if (!pub_hex.empty()) fprintf(w, "%s\"public_key_hex\":%s%s,", nl, sp, json_str(pub_hex).c_str());
             // split-key search: the partial key, the base it belongs to and the image - and no wif: a partial key is not importable
-            if (o.has_base) fprintf(w, "%s\"partial_key_hex\":%s%s,%s\"base_public_key\":%s%s,%s\"variant\":%s%d,", nl, sp, json_str(g.hex + 2).c_str(), nl, sp,
+            if (solana) fprintf(w, "%s\"seed_hex\":%s%s,%s\"keypair_base58\":%s%s,", nl, sp, json_str(g.hex).c_str(), nl, sp, json_str(keypair).c_str());   // (no wif)
+            else if (o.has_base) fprintf(w, "%s\"partial_key_hex\":%s%s,%s\"base_public_key\":%s%s,%s\"variant\":%s%d,", nl, sp, json_str(g.hex + 2).c_str(), nl, sp,
                                     json_str(base_hex).c_str(), nl, sp, variant);
             else fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,", nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str());
             fprintf(w, "%s\"format\":%s%s,%s\"pattern\":%s%s,%s"
@@ -920,6 +974,12 @@ int main(int argc, char **argv) {
 
     Opts o = parse(argc, argv);
     signal(SIGINT, on_sigint);
+    if ((o.cmd == "generate" || o.cmd == "range") && o.format == "solana") {
+        if (o.cmd == "range") die("'-f solana' cannot be used with 'range': a solana key is a seed whose scalar is its hash - there is no key range");
+        if (o.has_patterns_file) die("the argument '--patterns-file' cannot be used with '-f solana': pattern lists are not provided for this format");
+        if (!o.checkpoint.empty()) die("the argument '--checkpoint' cannot be used with '-f solana': checkpoints are not provided for this format");
+        if (o.has_base) die("the argument '--base-pubkey' cannot be used with '-f solana': a seed cannot be split");
+    }
     if ((o.cmd == "generate" || o.cmd == "range") && o.has_patterns_file) {
         if (o.has_pattern) die("the argument '--patterns-file' cannot be used with '--pattern'");
         vgen_filter *list = load_pattern_list(o, format_id(o.format));

@@ -197,4 +197,48 @@ VG_HD bool filter_eval_npub(const DevFilter *f, const u32 *payload) {
     return hit;
 }
 
+// ---- Solana addresses: Base58 of the 32-byte public key read as one big-endian number N, no version, no checksum ----
+// Functions of their own, as above.  A prefix of the string is a range of N (two at most per literal prefix: 43 and 44 characters),
+// its last k characters are N mod 58^k.
+
+// -1 / 0 / +1 for 256-bit big-endian word arrays
+VG_HD int cmp256(const u32 a[8], const u32 b[8]) {
+    int c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        int d = (a[i] > b[i]) - (a[i] < b[i]);
+        c = (c == 0) ? d : c;
+    }
+    return c;
+}
+
+// N mod m for the eight big-endian words of N, m < 2^32: eight 64-by-32-bit reduction steps.
+VG_HD u32 mod256(const u32 H[8], u32 m) {
+    u32 r = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r = (u32)((((u64)r << 32) | H[i]) % m);
+    return r;
+}
+
+// The prefilter (kinds 1, 3 and 7; a Base58 string has no masked tests) on a key's eight payload words in memory order.
+VG_HD bool filter_eval_sol(const DevFilter *f, const u32 *payload) {
+    const u32 kind = f->kind;
+    if (kind != DEVF_RANGES && kind != DEVF_SOL_RESIDUE) return kind != DEVF_MASKED;   // (ALL; HOST_ALL / DFA are judged elsewhere)
+    u32 H[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) H[i] = bswap32(payload[i]);
+    const u32 n = f->count, nr = kind == DEVF_RANGES ? n : f->chk_base;
+    bool in_range = kind == DEVF_SOL_RESIDUE && nr == 0;   // (ranges alone: an empty set - a prefix no 32-byte value has - accepts nothing)
+    for (u32 t = 0; t < nr; t++) {   // leading word first, as filter_eval_n's ranges
+        const DevFilterTest &T = f->tests[t];
+        const bool near = H[0] >= T.a[0] && H[0] <= T.b[0];
+        if (VG_ANY_LANE(near)) in_range = in_range || (near && cmp256(H, T.a) >= 0 && cmp256(H, T.b) <= 0);
+    }
+    if (kind == DEVF_RANGES || !in_range) return in_range;
+    const u32 r = mod256(H, f->witver);
+    bool hit = false;
+    for (u32 t = nr; t < n; t++) hit = hit || r == f->tests[t].a[0];
+    return hit;
+}
+
 }  // namespace vg

@@ -18,6 +18,9 @@ enum : int {
 // Nostr public key (NIP-19 npub): the BIP-340 x-only key itself, 32 bytes, no hash (not a format of the reference).  Format 10: the
 // numbers 8 and 9 stay unassigned - every entry point answers them as unknown formats, which callers and the suite rely on.
 constexpr int VGF_NOSTR{10};
+// Solana address: the Ed25519 public key of a 32-byte seed, 32 bytes, Base58 without checksum (not a format of the reference).  Format
+// 12; 11 stays unassigned like 8 and 9.  The only format on another curve: its key is the SEED, its kernels are ed_keys_kernel.
+constexpr int VGF_SOLANA{12};
 
 // the two formats whose payload is (derived from) the Ethereum account address: hex strings, both coordinates hashed
 constexpr bool vgf_is_eth(int fmt) { return fmt == VGF_ETHEREUM || fmt == VGF_ETHEREUM_CONTRACT; }
@@ -27,7 +30,7 @@ constexpr int vgf_string_format(int fmt) { return (fmt == VGF_ETHEREUM_CONTRACT 
 // point and stays what it is: a CREATE2 address has no point behind it)
 constexpr bool vgf_is_hex(int fmt) { return vgf_string_format(fmt) == VGF_ETHEREUM; }
 // payload words of a format: the 32-byte x-only keys (the taproot output key, the Nostr public key) take eight, everything else five
-constexpr int vgf_payload_words(int fmt) { return (fmt == VGF_P2TR || fmt == VGF_NOSTR) ? 8 : 5; }
+constexpr int vgf_payload_words(int fmt) { return (fmt == VGF_P2TR || fmt == VGF_NOSTR || fmt == VGF_SOLANA) ? 8 : 5; }
 // keys tested per curve point on a VGEN_FLAG_ENDO context: the six endomorphism / negation images, or - x-only keys, where (x, y)
 // and (x, -y) are one key - the three images x, beta x, beta^2 x
 constexpr uint32_t vgf_endo_images(int fmt) { return fmt == VGF_NOSTR ? 3u : 6u; }
@@ -46,6 +49,11 @@ enum : uint32_t {
     DEVF_SCORE = 6       // score specification (hex formats): the payloads are scored by kernels of their own (core/score_eval.h,
                          // ScoreTerms by value in the kernel arguments); the rest of DevFilter is unused
 };
+// VGF_SOLANA only (filter_eval_sol, core/filter_eval.h).  There DEVF_RANGES compares all eight big-endian words, and one more kind
+// tests the payload N, read as one big-endian number, modulo a power of 58 - the last characters of the address:
+//     DEVF_SOL_RESIDUE   (n_ranges == 0 or any r < n_ranges: lo_r <= N <= hi_r)  and  any t >= n_ranges: N mod modulus == tests[t].a[0]
+// with modulus = 58^k < 2^30 in `witver`, n_ranges in `chk_base` and `count` tests in all (fields no other kind of this format uses).
+constexpr uint32_t DEVF_SOL_RESIDUE = 7;
 
 constexpr uint32_t DEVF_MAX_TESTS = 64;
 constexpr uint32_t DEVF_FLAG_BECH32_CHK = 1u;   // masked tests also constrain the bech32 checksum
@@ -292,6 +300,22 @@ struct Create3ScoreArgs {
     unsigned long long first;
     uint32_t *out;               // payloads of hit lanes only, slot i at out + 5 i
     unsigned long long *hits;    // one bit per slot (batch / 64 words)
+};
+
+// ---- Solana (VGF_SOLANA; appended: no structure above changes) ------------------------------------------------------------------
+// Arguments of ed_keys_kernel: lane i tests seed i of the uploaded seeds (32 bytes each; lanes >= n have no key) or, seeds ==
+// nullptr, the digest core/rnd.h draws for (seed, stream, first + i) - every draw is a key.  batch lanes are launched either way.
+constexpr int ED_WG = 512;       // lanes per workgroup: its waves share one field inversion (kernels.hip)
+struct EdArgs {
+    const uint32_t *table;       // core/ed25519.h: ED_TABLE_WORDS words
+    const uint8_t *seeds;
+    uint32_t seed[6];            // RndSeed::w
+    uint32_t stream;
+    unsigned long long first;
+    uint32_t n;
+    uint32_t *payloads;          // slot i at payloads + 8 i: every slot (DUMP; zero where there is no key) or the slots of hit lanes only
+    unsigned long long *hits;    // PRE: the hit mask, one bit per slot (batch / 64 words)
+    const DevFilter *filter;     // PRE: the context's prefilter (kinds 1, 3, 7)
 };
 
 }  // namespace vg

@@ -49,6 +49,7 @@
 #define VG_HASH_BLOCKS 1   // core/dfa_eval.h: base58_checksum runs as a scheduled block too (hash_blocks.inc below)
 #include "../core/dfa_eval.h"
 #include "../core/ec.h"
+#include "../core/ed25519.h"
 #include "../core/filter_eval.h"
 #include "../core/hash.h"
 #include "../core/rnd.h"
@@ -2415,6 +2416,137 @@ hipError_t launch_ptab(const PtabArgs &a, int payload_words, hipStream_t stream)
 hipError_t launch_ptab_compact8(const PtabArgs &a, hipStream_t stream) {
     if (a.stride % 256 != 0 || a.count > a.stride || a.images == 0 || !a.payloads || !a.hits || !a.mhdr || !a.mrec) return hipErrorInvalidValue;
     hipLaunchKernelGGL((ptab_compact_kernel<8>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, a);
+    return hipGetLastError();
+}
+
+// ---- Solana (VGF_SOLANA): Ed25519 public keys from seeds -------------------------------------------------------------------------
+// The one format on another curve, and one whose keys cannot be walked: a wallet signs from the SEED and the scalar is
+// clamp(SHA-512(seed)[0..31]), so every candidate costs one SHA-512 block and one fixed-base multiplication (core/ed25519.h: 32
+// complete mixed additions over the 8-bit-window table, entry 0 the neutral element - no branch).  One candidate per lane:
+//   seed (uploaded, or drawn here by core/rnd.h - every draw is a key) -> SHA-512 -> clamp -> a*B = (X : Y : Z : T)
+//   -> 1/Z through an inversion the WORKGROUP shares -> x, y -> the 32 encoded bytes -> dump or prefilter.
+// Sharing the inversion: an inversion (254 squarings) costs about what the multiplication (224 products) does, and in a wave it
+// costs the same whether one lane or 64 invert.  So the ED_WG / 64 waves of a workgroup multiply their Z's together - a butterfly
+// of wave shuffles, in which every lane also collects the product of all the OTHER lanes' Z's (its cofactor) - then the waves'
+// totals meet in LDS, the first wave alone inverts the workgroup's total, and two products per lane undo the tree: 1/Z = (1/total) x
+// the wave's cofactor x the lane's cofactor.  One inversion's instructions per eight multiplications' worth, no global scratch,
+// no second kernel; Z is never 0 (the addition is complete), so neither is any product.
+//   DUMP   every payload to slot i (zero where the lane has no key)
+//   PRE    filter_eval_sol on the eight words in registers, the wave's ballot into the hit mask with one plain 64-bit store, the
+//          payloads of hit lanes only; ptab_compact_kernel<8> makes the records.  No atomics, no match_slot.
+
+VG_HD void ed_shfl_xor(fe25 &r, const fe25 &a, int mask) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.n[i] = (u32)__shfl_xor((int)a.n[i], mask, 64);
+}
+
+// After LEVELS steps: total = the product of the 2^LEVELS lanes of the group, co = the product of the group's other lanes.
+template <int LEVELS>
+__device__ __forceinline__ void ed_butterfly(fe25 &total, fe25 &co) {
+#pragma unroll
+    for (int l = 0; l < LEVELS; l++) {
+        fe25 s;
+        ed_shfl_xor(s, total, 1 << l);
+        if (l == 0) co = s;
+        else fe25_mul(co, co, s);
+        fe25_mul(total, total, s);
+    }
+}
+
+template <bool PRE>
+__global__ void __launch_bounds__(ED_WG) ed_keys_kernel(const EdArgs a) {
+    constexpr int WAVES = ED_WG / 64;
+    static_assert(WAVES == 8, "the second butterfly below has log2(WAVES) = 3 levels");
+    __shared__ u32 wave_total[WAVES][9], wave_inv[WAVES][9];
+    const u32 i = blockIdx.x * (u32)ED_WG + threadIdx.x;
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const bool has_key = i < a.n;
+    u32 s[8];   // the seed as eight big-endian words
+    if (a.seeds) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(a.seeds + (size_t)i * 32);
+        uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+        if (has_key) {
+            lo = src[0];
+            hi = src[1];
+        }
+        s[0] = bswap32(lo.x); s[1] = bswap32(lo.y); s[2] = bswap32(lo.z); s[3] = bswap32(lo.w);
+        s[4] = bswap32(hi.x); s[5] = bswap32(hi.y); s[6] = bswap32(hi.z); s[7] = bswap32(hi.w);
+    } else {
+        RndSeed rs;
+#pragma unroll
+        for (int k = 0; k < 6; k++) rs.w[k] = a.seed[k];
+        const u64 index = a.first + i;
+        u32 k[8];
+        rnd_scalar(rs, a.stream, (u32)index, (u32)(index >> 32), k);
+#pragma unroll
+        for (int j = 0; j < 8; j++) s[j] = k[7 - j];   // the digest in its natural order
+    }
+    u32 k[8];
+    ed_scalar_from_seed(s, k);
+    ed_pt p;
+    ed_mul_base(p, a.table, k);
+
+    fe25 total = p.Z, co;
+    ed_butterfly<6>(total, co);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) wave_total[wave][q] = total.n[q];
+    }
+    __syncthreads();
+    if (wave == 0) {
+        fe25 t, c, inv;
+        fe25_set_one(t);
+        if (lane < (u32)WAVES) {
+#pragma unroll
+            for (int q = 0; q < 9; q++) t.n[q] = wave_total[lane][q];
+        }
+        ed_butterfly<3>(t, c);
+        fe25_inv(inv, t);
+        fe25_mul(inv, inv, c);   // 1 / (the total of wave `lane`)
+        if (lane < (u32)WAVES) {
+#pragma unroll
+            for (int q = 0; q < 9; q++) wave_inv[lane][q] = inv.n[q];
+        }
+    }
+    __syncthreads();
+    fe25 zi, x, y;
+#pragma unroll
+    for (int q = 0; q < 9; q++) zi.n[q] = wave_inv[wave][q];
+    fe25_mul(zi, zi, co);
+    fe25_mul(x, p.X, zi);
+    fe25_mul(y, p.Y, zi);
+    u32 pl[8];
+    ed_encode(pl, x, y);
+#pragma unroll
+    for (int q = 0; q < 8; q++) pl[q] = has_key ? pl[q] : 0u;
+    uint4 *o = reinterpret_cast<uint4 *>(a.payloads + (size_t)i * 8);
+    if (!PRE) {
+        o[0] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
+        o[1] = make_uint4(pl[4], pl[5], pl[6], pl[7]);
+    } else {
+        const bool hit = has_key && filter_eval_sol(a.filter, pl);
+        const unsigned long long mask = __ballot(hit);
+        if (lane == 0) a.hits[i >> 6] = mask;
+        if (hit) {
+            o[0] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
+            o[1] = make_uint4(pl[4], pl[5], pl[6], pl[7]);
+        }
+    }
+}
+
+hipError_t launch_ed_keys(const EdArgs &a, uint32_t batch, const PtabArgs *compact, hipStream_t stream) {
+    if (batch == 0 || batch % ED_WG != 0 || a.n == 0 || a.n > batch || !a.table || !a.payloads) return hipErrorInvalidValue;
+    if (!compact) {
+        hipLaunchKernelGGL((ed_keys_kernel<false>), dim3(batch / ED_WG), dim3(ED_WG), 0, stream, a);
+        return hipGetLastError();
+    }
+    if (!a.hits || !a.filter || compact->payloads != a.payloads || compact->hits != a.hits || compact->stride != batch || compact->images != 1 ||
+        !compact->mhdr || !compact->mrec)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((ed_keys_kernel<true>), dim3(batch / ED_WG), dim3(ED_WG), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ptab_compact_kernel<8>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, *compact);
     return hipGetLastError();
 }
 

@@ -67,4 +67,7 @@ hipError_t launch_create2_score(const Create2ScoreArgs &a, uint32_t batch, const
 // 24 .. 88 when guarded.
 hipError_t launch_create3(const Create3Args &a, bool guarded, uint32_t batch, const PtabArgs *compact, hipStream_t stream);
 hipError_t launch_create3_score(const Create3ScoreArgs &a, bool guarded, uint32_t batch, const PtabArgs &compact, hipStream_t stream);
+// A Solana dispatch (VGF_SOLANA): one seed per thread, `batch` (a multiple of ED_WG) lanes of which the first a.n have a key; SHA-512,
+// the Ed25519 fixed-base multiplication, one inversion per workgroup.  `compact` as for launch_create2, over eight-word slots.
+hipError_t launch_ed_keys(const EdArgs &a, uint32_t batch, const PtabArgs *compact, hipStream_t stream);
 }  // namespace vg

@@ -1,6 +1,8 @@
 // encode.cpp — see encode.h.
 #include "encode.h"
 
+#include "ed_host.h"
+
 #include <ctype.h>
 #include <string.h>
 
@@ -367,6 +369,8 @@ std::string address_from_payload(uint32_t format, const uint8_t *payload) {
         return eip55_address(payload);
     case VGF_NOSTR:
         return nip19_encode("npub", payload);
+    case VGF_SOLANA:   // the 32 bytes as one big-endian number, no version, no checksum; a leading zero byte is a leading '1'
+        return base58_encode(payload, 32);
     default:
         return std::string();
     }
@@ -375,6 +379,7 @@ std::string address_from_payload(uint32_t format, const uint8_t *payload) {
 std::string key_to_wif(uint32_t format, const uint8_t key_be[32]) {
     if (vgf_is_eth((int)format)) return hex_lower(key_be, 32);
     if (format == VGF_NOSTR) return nip19_encode("nsec", key_be);
+    if (format == VGF_SOLANA) return hex_lower(key_be, 32);   // the seed (the 88-character keypair string: solana_keypair_base58)
     uint8_t buf[34];
     buf[0] = 0x80;
     memcpy(buf + 1, key_be, 32);
@@ -395,6 +400,10 @@ static void fe_to_be32(const fe &a, uint8_t out[32]) {
 }
 
 int payload_from_key(uint32_t format, const uint8_t key_be[32], uint8_t out[32]) {
+    if (format == VGF_SOLANA) {   // the key is an Ed25519 seed, any 32 bytes
+        ed_public_key(key_be, out);
+        return 32;
+    }
     Scalar k;
     scalar_from_be(k, key_be);
     if (!scalar_is_valid(k)) return 0;

@@ -5,6 +5,7 @@
 #include "../core/filter_eval.h"
 #include "../core/ptab_eval.h"
 #include "../core/score_eval.h"
+#include "ed_host.h"
 #include "encode.h"
 
 #include <string.h>
@@ -270,6 +271,231 @@ void derive_base58(const Dfa &d, uint8_t version, DevFilter &dev, double &sel) {
         }
         return;
     }
+}
+
+// ---- Solana: Base58 of the 32-byte public key read as one big-endian number N, no version byte, no checksum ---------------
+
+struct Range256 {
+    U256 lo, hi;   // inclusive
+};
+
+// a * 58 + d; false when the result passes 2^256 - 1
+bool mul58_add(U256 &a, uint32_t d) {
+    unsigned __int128 c = d;
+    for (int i = 0; i < 4; i++) {
+        c += (unsigned __int128)a.w[i] * 58u;
+        a.w[i] = (uint64_t)c;
+        c >>= 64;
+    }
+    return c == 0;
+}
+
+void to_be_words256(const U256 &a, uint32_t out[8]) {
+    for (int i = 0; i < 4; i++) {
+        out[7 - 2 * i] = (uint32_t)a.w[i];
+        out[6 - 2 * i] = (uint32_t)(a.w[i] >> 32);
+    }
+}
+
+// The exact ranges of N whose address starts with `p`: z leading '1's are z leading zero bytes, and what follows them are the
+// leading digits of a number of exactly 32 - z bytes - one range per digit count that fits (two at most: 58^d grows by 5.86 bits).
+void sol_prefix_ranges(const std::string &p, std::vector<Range256> &out) {
+    size_t z = 0;
+    while (z < p.size() && p[z] == '1') z++;
+    const std::string q = p.substr(z);
+    auto below_pow2 = [&](unsigned e) {   // 2^e - 1, e <= 256
+        U256 r;
+        for (int i = 0; i < 4; i++) r.w[i] = e >= 64u * (i + 1) ? ~0ull : e > 64u * i ? (1ull << (e - 64u * i)) - 1 : 0;
+        return r;
+    };
+    if (z > 32 || (z == 32 && !q.empty())) return;
+    if (q.empty()) {   // at least z leading zero bytes
+        out.push_back({U256(), below_pow2(8 * (32 - (unsigned)z))});
+        return;
+    }
+    const U256 vlo = U256::pow2(8 * (31 - (unsigned)z)), vhi = below_pow2(8 * (32 - (unsigned)z));
+    U256 lo, hi;
+    bool hi_sat = false;
+    for (char c : q) {
+        const int dg = b58_digit(c);
+        if (dg < 0 || !mul58_add(lo, (uint32_t)dg)) return;
+    }
+    hi = lo;
+    for (size_t m = q.size(); m <= 44; m++) {
+        const U256 l = umax(lo, vlo), h = umin(hi_sat ? vhi : hi, vhi);
+        if (cmp(l, h) <= 0) out.push_back({l, h});
+        if (cmp(lo, vhi) > 0) break;
+        if (!mul58_add(lo, 0)) break;   // from here on every candidate passes 2^256
+        if (!hi_sat && !mul58_add(hi, 57)) hi_sat = true;
+    }
+}
+
+void merge_ranges256(std::vector<Range256> &r) {
+    std::sort(r.begin(), r.end(), [](const Range256 &a, const Range256 &b) { return cmp(a.lo, b.lo) < 0; });
+    std::vector<Range256> out;
+    const U256 one = U256::from_u64(1);
+    for (auto &x : r) {
+        const bool top = !out.empty() && (~out.back().hi.w[0] | ~out.back().hi.w[1] | ~out.back().hi.w[2] | ~out.back().hi.w[3]) == 0;
+        if (!out.empty() && (top || cmp(x.lo, add(out.back().hi, one)) <= 0)) out.back().hi = umax(out.back().hi, x.hi);
+        else out.push_back(x);
+    }
+    r.swap(out);
+}
+
+// The device test of a Solana pattern: ranges of N from the accepted prefixes, residues of N modulo 58^k (k <= 5) from the accepted
+// last k characters, both when the pattern constrains both ends.  Always a superset: when the exact prefixes need more than
+// DEVF_MAX_TESTS ranges (classes, -i) the enumeration stops at the deepest level that fits, and the suffixes are those acceptable from ANY
+// reachable state (an address has 32 to 44 characters: where its last k begin is not known).
+void derive_solana(const Dfa &d, DevFilter &dev, double &sel) {
+    dev.kind = DEVF_HOST_ALL;
+    dev.count = 0;
+    sel = 1.0;
+    if (d.match_now[0]) {
+        dev.kind = DEVF_ALL;
+        return;
+    }
+    // (1) prefixes -> ranges, the deepest enumeration that fits
+    std::vector<Range256> ranges;
+    double prefix_sel = 1.0;
+    bool prefix_exact = false;
+    for (size_t depth = 1; depth <= 12; depth++) {   // (ascending: an unanchored pattern gives up after three levels, not after twelve)
+        std::vector<Prefix> prefixes;
+        if (!enumerate_prefixes(d, 0, B58, depth, 200000, prefixes)) break;
+        std::vector<Range256> r;
+        for (auto &p : prefixes) sol_prefix_ranges(p.s, r);
+        merge_ranges256(r);
+        if (r.size() > DEVF_MAX_TESTS) break;
+        double total = 0;
+        for (auto &x : r) total += to_double(sub(x.hi, x.lo)) + 1.0;
+        prefix_sel = total / 1.157920892373162e77;   // 2^256
+        prefix_exact = true;
+        for (auto &p : prefixes) prefix_exact = prefix_exact && p.absorbing;
+        ranges.swap(r);
+        if (prefix_exact) break;   // nothing deeper to learn
+    }
+    if (prefix_sel > 0.999999 && prefix_exact && ranges.size() == 1) {   // every address, decided by the prefixes alone
+        dev.kind = DEVF_ALL;
+        return;
+    }
+    const bool prefix_constrains = prefix_sel <= 0.2 || (prefix_exact && prefix_sel < 0.999999);
+
+    // (2) suffixes of k = 1 .. 5 characters -> residues mod 58^k
+    std::vector<uint32_t> all;
+    {
+        std::vector<uint8_t> seen(d.n_states, 0);
+        std::vector<uint32_t> stack{0};
+        seen[0] = 1;
+        while (!stack.empty()) {
+            const uint32_t st = stack.back();
+            stack.pop_back();
+            if (d.dead[st]) continue;
+            all.push_back(st);
+            if (d.match_now[st]) continue;
+            for (const char *a = B58; *a; a++) {
+                const uint32_t n = step(d, st, (unsigned char)*a);
+                if (!seen[n]) {
+                    seen[n] = 1;
+                    stack.push_back(n);
+                }
+            }
+        }
+        std::sort(all.begin(), all.end());
+    }
+    struct SuffixSet {
+        unsigned k = 0;
+        std::vector<uint32_t> residues;
+        double sel = 1.0;
+    };
+    std::vector<SuffixSet> sets;
+    // viable[r][s]: from state s some string of exactly r more characters ends in acceptance - prunes the enumeration
+    std::vector<std::vector<uint8_t>> viable(6, std::vector<uint8_t>(d.n_states, 0));
+    for (uint32_t st = 0; st < d.n_states; st++) viable[0][st] = d.match_now[st] || d.match_at_end[st];
+    for (unsigned r = 1; r <= 5; r++)
+        for (uint32_t st = 0; st < d.n_states; st++) {
+            if (d.match_now[st]) {
+                viable[r][st] = 1;
+                continue;
+            }
+            for (const char *a = B58; *a && !viable[r][st]; a++) viable[r][st] = viable[r - 1][step(d, st, (unsigned char)*a)];
+        }
+    for (unsigned k = 1; k <= 5; k++) {
+        struct Item {
+            std::vector<uint32_t> states;
+            uint32_t v;
+            unsigned len;
+        };
+        std::vector<Item> stack;
+        stack.push_back({all, 0, 0});
+        SuffixSet ss;
+        ss.k = k;
+        size_t visited = 0;
+        bool overflow = false;
+        while (!stack.empty() && !overflow) {
+            Item it = std::move(stack.back());
+            stack.pop_back();
+            if (++visited > 400000) overflow = true;
+            if (it.len == k) {
+                bool ok = false;
+                for (uint32_t st : it.states) ok = ok || d.match_now[st] || d.match_at_end[st];
+                if (ok) {
+                    ss.residues.push_back(it.v);
+                    if (ss.residues.size() > DEVF_MAX_TESTS) overflow = true;
+                }
+                continue;
+            }
+            for (uint32_t a = 0; a < 58; a++) {
+                std::vector<uint32_t> nxt;
+                for (uint32_t st : it.states) {
+                    const uint32_t n = d.match_now[st] ? st : step(d, st, (unsigned char)B58[a]);
+                    if (!d.dead[n] && viable[k - it.len - 1][n]) nxt.push_back(n);
+                }
+                if (nxt.empty()) continue;
+                std::sort(nxt.begin(), nxt.end());
+                nxt.erase(std::unique(nxt.begin(), nxt.end()), nxt.end());
+                stack.push_back({std::move(nxt), it.v * 58u + a, it.len + 1});
+            }
+        }
+        if (overflow) break;
+        ss.sel = (double)ss.residues.size();
+        for (unsigned i = 0; i < k; i++) ss.sel /= 58.0;
+        std::sort(ss.residues.begin(), ss.residues.end());
+        sets.push_back(std::move(ss));
+    }
+    // the most selective suffix set that leaves room for the ranges; without room for both, the better end alone
+    const SuffixSet *best = nullptr, *best_alone = nullptr;
+    for (auto &ss : sets) {
+        if (ss.sel > 0.2) continue;
+        if (!best_alone || ss.sel < best_alone->sel * (1.0 - 1e-9)) best_alone = &ss;   // (the shortest suffix of a selectivity)
+        if (prefix_constrains && ranges.size() + ss.residues.size() <= DEVF_MAX_TESTS && (!best || ss.sel < best->sel * (1.0 - 1e-9))) best = &ss;
+    }
+    const SuffixSet *use_s = nullptr;
+    bool use_p = prefix_constrains;
+    if (prefix_constrains && best) use_s = best;
+    else if (best_alone && (!prefix_constrains || best_alone->sel < prefix_sel)) {
+        use_s = best_alone;
+        use_p = false;
+    }
+    if (!use_p && !use_s) return;   // DEVF_HOST_ALL: correct and slow
+    uint32_t n = 0;
+    if (use_p)
+        for (auto &x : ranges) {
+            to_be_words256(x.lo, dev.tests[n].a);
+            to_be_words256(x.hi, dev.tests[n].b);
+            n++;
+        }
+    sel = use_p ? prefix_sel : 1.0;
+    if (use_s) {
+        dev.kind = DEVF_SOL_RESIDUE;
+        dev.chk_base = n;
+        uint32_t m = 1;
+        for (unsigned i = 0; i < use_s->k; i++) m *= 58u;
+        dev.witver = m;
+        for (uint32_t r : use_s->residues) dev.tests[n++].a[0] = r;
+        sel *= use_s->sel;
+    } else {
+        dev.kind = DEVF_RANGES;
+    }
+    dev.count = n;
 }
 
 // ---- fixed-length symbol strings (Bech32 P2WPKH, hex Ethereum) ---------------------------------------------
@@ -724,6 +950,9 @@ bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t 
         if (out.dev.kind == DEVF_HOST_ALL && build_dfa_blob(out.dfa, "npub1", BECH32, out.dfa_blob)) out.dev.kind = DEVF_DFA;
         break;
     }
+    case VGF_SOLANA:
+        derive_solana(out.dfa, out.dev, out.selectivity);
+        break;
     case VGF_P2TR: {
         // bc1p + 52 data symbols (256 bits + 4 pad bits) + 6 Bech32m checksum symbols
         const SymSpec sp = {"bc1p", BECH32, 5, 52, 6, 256};
@@ -1043,6 +1272,8 @@ bool payload_from_address(uint32_t format, const std::string &address, uint8_t o
         return true;   // any casing decodes; the patterns' automata judge the string itself
     } else if (format == VGF_NOSTR) {
         return nip19_decode("npub", a, out);   // (strict: header, length, case, pad bits, checksum)
+    } else if (format == VGF_SOLANA) {
+        return solana_decode(a, out);          // (strict: the alphabet, exactly 32 bytes)
     } else if (format == VGF_P2WPKH || format == VGF_P2TR) {
         const size_t n_data = format == VGF_P2TR ? 52 : 32, len = 4 + n_data + 6;
         if (a.size() != len) return false;

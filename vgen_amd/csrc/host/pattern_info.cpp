@@ -17,7 +17,8 @@ Charset charset_of(unsigned format) {
     switch ((int)format) {
     case VGF_P2PKH:
     case VGF_P2PKH_UNCOMPRESSED:
-    case VGF_P2SH_P2WPKH: return Charset::Base58;
+    case VGF_P2SH_P2WPKH:
+    case VGF_SOLANA: return Charset::Base58;   // (no constant prefix: pattern_difficulty's `shared` stays 0)
     case VGF_P2WPKH:
     case VGF_P2TR:
     case VGF_NOSTR: return Charset::Bech32;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../../include/vgen_hip.h"
+#include "ed_host.h"
 #include "encode.h"
 #include "filter.h"
 #include "scalar.h"
@@ -101,6 +102,24 @@ inline bool make_match(const vgen_filter &flt, uint32_t format, const BatchKeys 
                 const uint8_t *payload, const Scalar *end, LiteMatch &g, uint32_t batch = 0, uint32_t images = 1) {
     std::string addr = address_from_payload(format, payload);
     if (addr.empty() || addr.size() >= sizeof g.address || !filter_accepts(flt, addr, payload)) return false;   // pattern.matches, gpu.rs:1069
+    if (format == VGF_SOLANA) {
+        // The key is the SEED the stream drew for this candidate (every draw is one: no range test).  Its public key is re-derived here
+        // with the host build of the device's headers, and a candidate whose payload differs is dropped: one multiplication per MATCH.
+        if (!bk.random) return false;   // (nothing walks this format)
+        const uint64_t at = bk.first_index + index;
+        u32 d[8];
+        rnd_scalar(bk.seed, bk.stream, (u32)at, (u32)(at >> 32), d);
+        uint8_t mine[32];
+        for (int i = 0; i < 8; i++)
+            for (int b = 0; b < 4; b++) g.key[4 * i + b] = (uint8_t)(d[7 - i] >> (8 * (3 - b)));
+        ed_public_key(g.key, mine);
+        if (memcmp(mine, payload, 32) != 0) {
+            if (bk.dropped) bk.dropped->fetch_add(1, std::memory_order_relaxed);
+            return false;
+        }
+        memcpy(g.address, addr.c_str(), addr.size() + 1);
+        return true;
+    }
     Scalar k;
     const uint32_t variant = images > 1 ? index / batch : 0;
     if (images > 1) index %= batch;

@@ -13,6 +13,8 @@
 
 #include "core/hash.h"
 #include "device/launch.h"
+#include "core/ed25519.h"
+#include "host/ed_host.h"
 #include "host/host_ec.h"
 
 namespace vg {
@@ -71,6 +73,8 @@ void fe_canon_neg(fe &r, const fe &a) {
 size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 void release_gtab(vgen_ctx *c);   // (defined with the generator-table cache below)
+void release_edtab(vgen_ctx *c);  // (the Ed25519 table's cache, beside the Solana dispatches)
+int acquire_edtab(vgen_ctx *c);
 bool mem_allows(vgen_ctx *c, uint64_t extra, bool table, bool by_name, std::string *why);   // (the memory policy, same place)
 
 // Frame i's stream, created on first use (a stream costs ~5-8 ms: a scan's first dispatches should be running while
@@ -270,12 +274,16 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
         err = "device index out of range";
         return VGEN_E_NODEVICE;
     }
-    if (p->format > VGF_ETHEREUM_CREATE2 && p->format != VGF_NOSTR) {
+    if (p->format > VGF_ETHEREUM_CREATE2 && p->format != VGF_NOSTR && p->format != VGF_SOLANA) {
         err = "unknown address format";
         return VGEN_E_INVALID;
     }
     if (p->format == VGF_ETHEREUM_CREATE2 && (p->flags & VGEN_FLAG_ENDO)) {
         err = "VGEN_FLAG_ENDO: a CREATE2 search has no curve points to take images of";
+        return VGEN_E_UNSUPPORTED;
+    }
+    if (p->format == VGF_SOLANA && (p->flags & VGEN_FLAG_ENDO)) {
+        err = "VGEN_FLAG_ENDO: the endomorphism images belong to secp256k1; a solana search has none";
         return VGEN_E_UNSUPPORTED;
     }
     const bool trace = getenv("VGEN_TRACE_CREATE") != nullptr;
@@ -361,6 +369,23 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
         c->create2_set = create2_set;
         c->create2_dispatch = create2_dispatch;
         c->create3_set = create3_set;
+        *out = c;
+        return VGEN_OK;
+    }
+    if (c->format == VGF_SOLANA) {
+        // another curve: none of the secp256k1 scratch, offset table or generator tables - the filter program, the match rings and the
+        // device's Ed25519 table here, dump, list and seed buffers at their first use
+        const uint64_t fixed = sizeof(DevFilter) + (uint64_t)up256(match_bytes(c->match_cap)) * c->frames;
+        if (c->mem_budget && fixed + ED_TABLE_WORDS * sizeof(uint32_t) > c->mem_budget)
+            return bail(VGEN_E_NOMEM, "device_mem_budget_bytes " + std::to_string(c->mem_budget) + " does not cover the frames and the table: " +
+                                          std::to_string(fixed + ED_TABLE_WORDS * sizeof(uint32_t)) + " bytes");
+        e = hipMalloc((void **)&c->d_filter, sizeof(DevFilter));
+        if (e != hipSuccess) return bail(VGEN_E_NOMEM, std::string("hipMalloc(filter): ") + hipGetErrorString(e));
+        c->frames_bytes += sizeof(DevFilter);
+        if (int rc = rt_set_match_cap(c, c->match_cap)) return bail(rc, c->err);
+        lap("filter + match rings");
+        if (int rc = acquire_edtab(c)) return bail(rc, c->err);
+        lap("ed25519 table");
         *out = c;
         return VGEN_OK;
     }
@@ -522,6 +547,8 @@ void rt_destroy(vgen_ctx *c) {
     if (c->d_rtab) (void)hipFree(c->d_rtab);
     if (c->d_gtab) (void)hipFree(c->d_gtab);
     release_gtab(c);                              // the wide table is shared per device: freed with its last user
+    release_edtab(c);                             // ... and so is the Ed25519 table
+    if (c->d_seed_slab) (void)hipFree(c->d_seed_slab);
     if (c->d_chk_lut) (void)hipFree(c->d_chk_lut);
     if (c->d_dfa) (void)hipFree(c->d_dfa);
     if (c->d_filter) (void)hipFree(c->d_filter);
@@ -617,6 +644,7 @@ bool list_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind ==
 bool score_mode(const vgen_ctx *c) { return c->have_filter && c->h_filter.kind == DEVF_SCORE; }
 bool deferred_filter(const vgen_ctx *c) {
     // ... and so do the x-only Nostr keys (xonly_bwd_kernel's payload form, then the eight-word payload_filter8_kernel<FULL>)
+    // (a Solana filter is never an automaton: its compiler has kinds 0, 1, 3 and 7 only)
     return (c->format == VGF_ETHEREUM_CONTRACT || ((c->format == VGF_ETHEREUM_CREATE2 || c->format == VGF_NOSTR) && c->h_filter.kind == DEVF_DFA)) && c->have_filter && !dump_mode(c) &&
            !list_mode(c) && !score_mode(c);
 }
@@ -624,7 +652,8 @@ bool deferred_filter(const vgen_ctx *c) {
 // then the compaction alone.
 // The Nostr per-key kernels do the same (xonly_bwd_kernel<PRE>, keys_xonly_kernel<PRE>): prefilter in registers, an atomic-free hit mask.
 bool inline_filter(const vgen_ctx *c) {
-    return (c->format == VGF_ETHEREUM_CREATE2 || c->format == VGF_NOSTR) && c->have_filter && !dump_mode(c) && !list_mode(c) && !deferred_filter(c) && !score_mode(c);
+    return (c->format == VGF_ETHEREUM_CREATE2 || c->format == VGF_NOSTR || c->format == VGF_SOLANA) && c->have_filter && !dump_mode(c) && !list_mode(c) &&
+           !deferred_filter(c) && !score_mode(c);
 }
 
 // The pattern-list buffers of every frame: the payloads of a dispatch (20 B per key, x 6 on an endomorphism context, 32 B for
@@ -1338,6 +1367,114 @@ int enqueue_keys(vgen_ctx *c, vgen_ctx::Frame &f, const uint8_t *keys_dev, const
     return finish_dispatch(c, f, dump, endo_now ? (uint64_t)n * vgf_endo_images((int)c->format) : n, endo_now);
 }
 
+// ---- Solana (VGF_SOLANA) ----------------------------------------------------------------------------------------------------
+// The Ed25519 table: 917 504 bytes, built by the host build of core/ed25519.h (host/ed_host.h; ~10 ms, once per process), uploaded
+// once per device and shared by the process's contexts there.  Reference-counted; the last context to go frees it.
+struct EdTabShared {
+    int device;
+    uint32_t *tab;
+    uint32_t refs;
+};
+struct EdTabCache {
+    std::mutex mu;
+    std::vector<EdTabShared> tabs;
+};
+EdTabCache &edtab_cache() {
+    static EdTabCache *g = new EdTabCache();   // (never destroyed, as the generator-table cache)
+    return *g;
+}
+
+int acquire_edtab(vgen_ctx *c) {
+    EdTabCache &g = edtab_cache();
+    std::lock_guard<std::mutex> lk(g.mu);
+    for (EdTabShared &t : g.tabs)
+        if (t.device == c->device) {
+            t.refs++;
+            c->d_edtab = t.tab;
+            return VGEN_OK;
+        }
+    uint32_t *d = nullptr;
+    if (hipMalloc((void **)&d, ED_TABLE_WORDS * sizeof(uint32_t)) != hipSuccess) return c->fail(VGEN_E_NOMEM, "ed25519 table allocation failed");
+    if (int rc = upload(c, d, ed_host_table(), ED_TABLE_WORDS * sizeof(uint32_t))) {
+        (void)hipFree(d);
+        return rc;
+    }
+    g.tabs.push_back(EdTabShared{c->device, d, 1});
+    c->d_edtab = d;
+    return VGEN_OK;
+}
+
+void release_edtab(vgen_ctx *c) {
+    if (!c->d_edtab) return;
+    EdTabCache &g = edtab_cache();
+    std::lock_guard<std::mutex> lk(g.mu);
+    for (size_t i = 0; i < g.tabs.size(); i++) {
+        EdTabShared &t = g.tabs[i];
+        if (t.device != c->device || t.tab != c->d_edtab) continue;
+        if (--t.refs == 0) {
+            (void)hipFree(t.tab);
+            g.tabs.erase(g.tabs.begin() + (long)i);
+        }
+        break;
+    }
+    c->d_edtab = nullptr;
+}
+
+// The frames' seed buffers of vgen_dispatch_keys: batch x 32 bytes each, one allocation at first use.
+int ensure_seed_slab(vgen_ctx *c) {
+    if (c->d_seed_slab) return VGEN_OK;
+    const size_t per = up256((size_t)c->batch * 32);
+    std::string refused;
+    if (!mem_allows(c, (uint64_t)per * c->frames, false, false, &refused)) return c->fail(VGEN_E_NOMEM, "seed buffers: " + refused);
+    HIP_TRY(c, hipMalloc((void **)&c->d_seed_slab, per * c->frames));
+    c->mode_bytes += (uint64_t)per * c->frames;
+    for (uint32_t i = 0; i < c->frames; i++) c->fr[i].d_keys = c->d_seed_slab + per * i;
+    return VGEN_OK;
+}
+
+// One kernel per dispatch (and the compaction behind its prefilter form), on the frame's own stream: uploaded seeds (seeds_dev) or
+// the stream's draws first .. first + batch - 1.
+int enqueue_ed(vgen_ctx *c, uint32_t frame, const uint8_t *seeds_dev, const RndSeed *seed, uint32_t stream, uint64_t first, uint32_t n) {
+    vgen_ctx::Frame &f = c->fr[frame];
+    if (!c->d_edtab) return c->fail(VGEN_E_STATE, "the context has no ed25519 table");
+    EdArgs a;
+    memset(&a, 0, sizeof a);
+    a.table = c->d_edtab;
+    a.seeds = seeds_dev;
+    if (seed) memcpy(a.seed, seed->w, sizeof a.seed);
+    a.stream = stream;
+    a.first = first;
+    a.n = n;
+    const bool dump = dump_mode(c);
+    PtabArgs p;
+    memset(&p, 0, sizeof p);
+    if (dump) {
+        if (int rc = ensure_dump_frame(c, frame)) return rc;
+        a.payloads = f.d_dump;
+    } else {
+        if (!inline_filter(c)) return c->fail(VGEN_E_UNSUPPORTED, "a solana context takes single patterns only (no lists, no scores)");
+        if (!f.d_list) return c->fail(VGEN_E_STATE, "the context's filter has no list buffers");   // (made by vgen_set_filter)
+        a.payloads = f.d_list;
+        a.hits = f.d_hits;
+        a.filter = c->d_filter;
+        p.payloads = f.d_list;
+        p.hits = f.d_hits;
+        p.mhdr = reinterpret_cast<DevMatchHeader *>(f.d_match);
+        p.mrec = reinterpret_cast<DevMatch *>(f.d_match + sizeof(DevMatchHeader));
+        p.stride = c->batch;
+        p.count = n;
+        p.images = 1;
+        p.match_base = f.match_base;
+        p.match_cap = c->match_cap;
+    }
+    if (c->timing) {
+        HIP_TRY(c, hipEventRecord(f.ev_start, f.s));
+        HIP_TRY(c, hipEventRecord(f.ev_mid, f.s));
+    }
+    HIP_TRY(c, launch_ed_keys(a, c->batch, dump ? nullptr : &p, f.s));
+    return finish_dispatch(c, f, dump, n, false);
+}
+
 }  // namespace
 
 // A CREATE2 context walks salts, not keys: the key dispatches refuse it.
@@ -1347,6 +1484,8 @@ static int refuse_create2(vgen_ctx *c, const char *what) {
 
 int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
     if (c->format == VGF_ETHEREUM_CREATE2) return refuse_create2(c, "vgen_dispatch");
+    if (c->format == VGF_SOLANA)
+        return c->fail(VGEN_E_UNSUPPORTED, "vgen_dispatch: a solana key is a seed and its scalar a hash of it - there is no walk; use vgen_dispatch_random / vgen_dispatch_keys");
     if (frame >= c->frames || !start_key_be) return c->fail(VGEN_E_INVALID, "bad frame index / key");
     vgen_ctx::Frame &f = c->fr[frame];
     if (f.in_flight) return c->fail(VGEN_E_STATE, "frame already has a dispatch in flight");
@@ -1472,6 +1611,12 @@ int rt_dispatch_keys(vgen_ctx *c, uint32_t frame, const uint8_t *keys_be, uint32
     if (c->injected_fault()) return c->fail(VGEN_E_HIP, "injected device failure (vgen_debug_fail_after)");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = ensure_frame(c, frame)) return rc;
+    if (c->format == VGF_SOLANA) {   // keys_be holds seeds
+        if (int rc = ensure_seed_slab(c)) return rc;
+        HIP_TRY(c, hipMemcpyAsync(f.d_keys, keys_be, (size_t)n * 32, hipMemcpyHostToDevice, f.s));
+        memset(&f.start, 0, sizeof f.start);
+        return enqueue_ed(c, frame, f.d_keys, nullptr, 0, 0, n);
+    }
     if (int rc = ensure_keys_slab(c)) return rc;
     HIP_TRY(c, hipMemcpyAsync(f.d_keys, keys_be, (size_t)n * 32, hipMemcpyHostToDevice, f.s));
     memset(&f.start, 0, sizeof f.start);
@@ -1605,6 +1750,10 @@ int rt_dispatch_random(vgen_ctx *c, uint32_t frame, const RndSeed &seed, uint32_
     if (c->injected_fault()) return c->fail(VGEN_E_HIP, "injected device failure (vgen_debug_fail_after)");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = ensure_frame(c, frame)) return rc;
+    if (c->format == VGF_SOLANA) {   // the seeds are drawn inside the kernel: no key buffer
+        memset(&f.start, 0, sizeof f.start);
+        return enqueue_ed(c, frame, nullptr, &seed, stream, first_index, c->batch);
+    }
     if (int rc = ensure_keys_slab(c)) return rc;
     memset(&f.start, 0, sizeof f.start);
     // the scalars are drawn into the frame's key buffer by a small kernel; from there on the dispatch is vgen_dispatch_keys'
@@ -1740,7 +1889,7 @@ int rt_get_memory(const vgen_ctx *c, vgen_memory_info *out) {
     out->table_bits = c->d_gtab16 ? c->gtab_bits : c->d_gtab ? 8u : 0u;
     out->frames_bytes = c->frames_bytes;
     out->mode_bytes = c->mode_bytes;
-    out->table_bytes = gtab_held_bytes(c);
+    out->table_bytes = gtab_held_bytes(c) + (c->d_edtab ? ED_TABLE_WORDS * sizeof(uint32_t) : 0);   // (the Ed25519 table of a Solana context)
     out->pinned_host_bytes = c->pinned_bytes;
     out->budget_bytes = c->mem_budget;
     size_t free_b = 0, total_b = 0;

@@ -110,6 +110,10 @@ struct vgen_ctx {
     size_t ptab_bytes = 0;               // allocated size of d_ptab
     vg::DevPtab ptab{};                  // device pointers into d_ptab
     uint8_t *d_list_slab = nullptr;
+    // VGF_SOLANA: the Ed25519 fixed-base table (core/ed25519.h; built by the host, uploaded once per device and shared by the process's
+    // contexts there: a reference, not owned) and the frames' seed buffers of vgen_dispatch_keys (Frame::d_keys; made at first use)
+    uint32_t *d_edtab = nullptr;
+    uint8_t *d_seed_slab = nullptr;
 
     struct Frame {
         hipStream_t s = nullptr;         // this frame's stream (owned by the context): carries the whole dispatch chain

@@ -303,7 +303,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
     // This is a PREFERENCE: the caller bounds it (cfg->table_bits_max, vgen_params.table_bits / device_mem_budget_bytes), the runtime
     // checks it against the device's free memory, builds the wider table in the background while this loop dispatches on the one
     // it has, and takes it into use when it is complete (runtime.cpp) — the scan never waits for a table.
-    if (random_keys || ctx->format == VGF_P2TR) {
+    if ((random_keys || ctx->format == VGF_P2TR) && ctx->format != VGF_SOLANA) {   // (a Solana context has no generator table to widen)
         // (a count-limited scan whose pattern has no selectivity estimate — the whole DFA on the device — is taken for short)
         double keys = cfg->count == UINT64_MAX ? 1e30 : 0.0;
         if (!host_all && flt.selectivity > 0 && cfg->count != UINT64_MAX) keys = (double)cfg->count / flt.selectivity;
@@ -436,7 +436,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
     // A scan of the scalar-multiplication paths that turns out LONG although nothing said so up front (no selectivity estimate, a
     // count that keeps not being reached): after 5 s it asks for the 29-bit signed table (+12.5 % once it is there) and simply goes
     // on — the runtime builds it behind the dispatches (round 4 drained the frames and paused 0.7 - 2.3 s here).
-    const bool table_path = random_keys || ctx->format == VGF_P2TR;
+    const bool table_path = (random_keys || ctx->format == VGF_P2TR) && ctx->format != VGF_SOLANA;
     const auto scan_t0 = std::chrono::steady_clock::now();
     bool upgrade_asked = false;
     auto may_launch = [&]() { return can_dispatch() && !stopped() && !sink.done(); };
@@ -696,6 +696,24 @@ static bool any_create2(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_scan_config 
     return any;
 }
 
+// Solana scans (VGF_SOLANA, context or configuration): a seed has no neighbour, so the scan IS the random-key loop - the flag is implied -
+// and there is no range to start or end; checkpoints are not provided yet.  VGEN_OK, or the refusal.
+static int solana_scan_rules(vgen_ctx **ctxs, uint32_t n_ctx, vgen_scan_config &c, const char *what) {
+    bool any = c.format == VGF_SOLANA;
+    for (uint32_t i = 0; i < n_ctx; i++) any = any || ctxs[i]->format == VGF_SOLANA;
+    if (!any) return VGEN_OK;
+    vgen_ctx *c0 = ctxs[0];
+    // (all or none: the flag below must not reach a context of another format, nor a Solana context a scan of another)
+    for (uint32_t i = 0; i < n_ctx; i++)
+        if (ctxs[i]->format != VGF_SOLANA || c.format != VGF_SOLANA)
+            return c0->fail(VGEN_E_INVALID, std::string(what) + ": a solana scan needs the solana format (12) in the configuration and on every context");
+    if (c.has_start || c.has_end)
+        return c0->fail(VGEN_E_UNSUPPORTED, std::string(what) + ": a solana key is a seed and its scalar a hash of it - there is no key range (has_start / has_end)");
+    if (c.checkpoint_path) return c0->fail(VGEN_E_UNSUPPORTED, std::string(what) + ": checkpoints are not provided for the solana format");
+    c.flags |= VGEN_SCAN_RANDOM_KEYS;
+    return VGEN_OK;
+}
+
 // ABI 4's vgen_scan_config, or ABI 3's 136 bytes (no table_bits_max: no cap): -> the full structure, fields beyond the caller's zero.
 static bool normalise_scan_config(const vgen_scan_config *in, vgen_scan_config &full) {
     constexpr uint32_t CONFIG_ABI3 = 136;
@@ -739,6 +757,7 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
     if (!ctx || !pattern || !out || !normalise_scan_config(cfg_in, c)) return VGEN_E_INVALID;
     memset(out, 0, sizeof *out);
     if (ctx->format == VGF_ETHEREUM_CREATE2 || c.format == VGF_ETHEREUM_CREATE2) return refuse_create2(ctx, "vgen_scan");
+    if (int rc = solana_scan_rules(&ctx, 1, c, "vgen_scan")) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     vgen_filter flt;
     std::string err;
@@ -1004,6 +1023,7 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
     vgen_scan_config cfg_full;
     if (!pattern || !multi_args(ctxs, n_ctx, cfg_in, cfg_full, out)) return VGEN_E_INVALID;
     if (any_create2(ctxs, n_ctx, cfg_full)) return refuse_create2(ctxs[0], "vgen_scan_multi");
+    if (int rc = solana_scan_rules(ctxs, n_ctx, cfg_full, "vgen_scan_multi")) return rc;
     const vgen_scan_config *cfg = &cfg_full;
     vgen_filter flt;
     std::string err;
@@ -1021,6 +1041,8 @@ extern "C" int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter
     vgen_scan_config cfg_full;
     if (!list || !multi_args(ctxs, n_ctx, cfg_in, cfg_full, out)) return VGEN_E_INVALID;
     if (any_create2(ctxs, n_ctx, cfg_full)) return refuse_create2(ctxs[0], "vgen_scan_list");
+    if (cfg_full.format == VGF_SOLANA || list->format == VGF_SOLANA || ctxs[0]->format == VGF_SOLANA)
+        return ctxs[0]->fail(VGEN_E_UNSUPPORTED, "vgen_scan_list: pattern lists are not provided for the solana format");
     if (!list->list) return ctxs[0]->fail(VGEN_E_INVALID, "vgen_scan_list needs a pattern list (vgen_filter_compile_list)");
     if (cfg_full.format != list->format) return ctxs[0]->fail(VGEN_E_INVALID, "scan format differs from the pattern list's format");
     cfg_full.case_insensitive = list->case_insensitive ? 1 : 0;   // the list carries it
