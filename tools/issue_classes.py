@@ -6,7 +6,9 @@ behind it, ONE full-rate instruction of another wave.
   X  exclusive   v_mad_u64_u32, v_mul_lo / hi_u32, the 64-bit shifts and adds (v_lshl_add_u64, v_lshrrev_b64): the slot holds nothing else
   C  half rate   v_alignbit, v_add3, v_perm, v_bfe, v_lshlrev_b32, compares, carry-flag adds ...: first place only, a full-rate instruction may follow
   S  full rate   add / sub / logic / right shift / mov, v_bitop3 (in either encoding): either place
-so a key needs at least  X + max(C, (C + S) / 2)  slots.  usage: python tools/issue_classes.py > profiles/r05_issue_classes.json"""
+so a key needs at least  X + max(C, (C + S) / 2)  slots.  usage: python tools/issue_classes.py > profiles/r05_issue_classes.json
+--by-opcode: instead, the class X and class C instructions of the key loop OUTSIDE the generated hash block, per key by opcode — the first places
+the point arithmetic, the canonicalisation, the key's words and the prefilter take (the block's own are device/hashgen.py's)."""
 import json
 import os
 import re
@@ -47,8 +49,14 @@ def classify(line):
     return None
 
 
-def stream(path):
-    """-> (tokens of the per-pair part of the key loop, tokens of the per-key part: point arithmetic + hash block + the prefilter's fast path)."""
+def opcode(line):
+    m = re.match(r"([a-z_0-9]+)", line)
+    return re.sub(r"_(e32|e64|sdwa|dpp)$", "", m.group(1)) if m else None
+
+
+def stream(path, by_opcode=False):
+    """-> (tokens of the per-pair part of the key loop, tokens of the per-key part: point arithmetic + hash block + the prefilter's fast path).
+    by_opcode: -> {class: {opcode: instructions per key}} of both parts without the hash block."""
     txt = open(path).read()
     s = txt.index(SYM)
     b = [l.strip() for l in txt[s:txt.index("s_endpgm", s)].split("\n")]
@@ -56,13 +64,29 @@ def stream(path):
     inner = [i for i, l in enumerate(b) if l.startswith(".LBB") and "Depth=2" in l][0]
     starts = [i for i, l in enumerate(b) if "ASMSTART" in l]
     ends = [i for i, l in enumerate(b) if "ASMEND" in l]
-    hash_end = max(zip(starts, ends), key=lambda p: p[1] - p[0])[1]
+    hash_start, hash_end = max(zip(starts, ends), key=lambda p: p[1] - p[0])
+    if by_opcode:
+        table = {"X": {}, "C": {}}
+        parts = ((b[outer:inner], 0.5), (b[inner:hash_start] + b[hash_end:hash_end + 30], 1.0))
+        for lines, weight in parts:
+            for l in lines:
+                if l and not l.startswith((".", ";")) and classify(l) in table:
+                    t = table[classify(l)]
+                    t[opcode(l)] = t.get(opcode(l), 0.0) + weight
+        return table
     code = lambda lines: [t for t in (classify(l) for l in lines if l and not l.startswith((".", ";"))) if t]
     return code(b[outer:inner]), code(b[inner:hash_end + 30])
 
 
 def main():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "vgen_amd", "csrc"), "../../build/lib/device/kernels.s"])
+    if "--by-opcode" in sys.argv[1:]:
+        table = stream(os.path.join(ROOT, "build", "lib", "device", "kernels.s"), by_opcode=True)
+        for c in "XC":
+            print("class %s outside the hash block: %.1f per key" % (c, sum(table[c].values())))
+            for op, n in sorted(table[c].items(), key=lambda kv: -kv[1]):
+                print("  %-22s %7.1f" % (op, n))
+        return
     per_pair, per_key = stream(os.path.join(ROOT, "build", "lib", "device", "kernels.s"))
     count = {c: (per_pair.count(c) / 2.0 + per_key.count(c)) for c in "XCSNP"}
     valu = count["X"] + count["C"] + count["S"]

@@ -95,17 +95,36 @@ VG_HD u32 fe_opaque_() {
 #endif
 }
 
+// 2 a for a squaring's cross terms.  LEAN on the device: a full-rate v_add_u32 a, a — hipcc turns a + a back into the
+// shift, and v_lshlrev_b32 issues at half rate (it takes the first place of an issue slot, tools/issue_classes.py).
+template <bool LEAN>
+VG_HD u32 fe_twice_(u32 a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (LEAN) {
+        u32 r;
+        asm("v_add_u32 %0, %1, %1" : "=v"(r) : "v"(a));
+        return r;
+    }
+#endif
+    return a << 1;
+}
+
 // One routine for a*b (+c) and a^2 (+c).  The high columns are produced first (k = 16 .. 9) and folded at
 // once, so only ten accumulators D_0..D_9 plus the column in hand are alive (22 registers instead of 34).
-template <bool SQR>
+// LEAN (the key loop of the sequential scan kernels, which is bound by first places of the issue slots): the addend c
+// is the accumulators' starting value instead of nine multiply-adds by an opaque 1 after the fold, and a squaring doubles
+// its limbs at full rate (fe_twice_).  Same 64-bit sums either way: the results are bit-identical.  A flag and not the
+// only form because this file is compiled into every kernel: some of those that sit at their register cap lose a
+// register or two to the other order (profiles/r05_kernel_resources.txt holds the ceilings).
+template <bool SQR, bool LEAN = false>
 VG_HD void fe_mul_columns_(fe &r, const fe &a, const fe &b, const fe *c3) {
     const u32 R1 = fe_opaque_<FE_R1>(), R0x8 = FE_R0 * 8u, R1x8 = fe_opaque_<FE_R1 * 8u>();
     u32 d[9];   // SQR: doubled limbs for the cross terms (a of magnitude 1)
 #pragma unroll
-    for (int i = 0; i < 9; i++) d[i] = SQR ? (a.n[i] << 1) : 0u;
-    u64 D[10];
+    for (int i = 0; i < 9; i++) d[i] = SQR ? fe_twice_<LEAN>(a.n[i]) : 0u;
+    u64 D[10];   // LEAN: 2^31 per limb of c against 2^63.76: no effect on the bounds
 #pragma unroll
-    for (int k = 0; k < 10; k++) D[k] = 0;
+    for (int k = 0; k < 10; k++) D[k] = (LEAN && c3 && k < 9) ? (u64)c3->n[k] : 0;
 #pragma unroll
     for (int k = 16; k >= 0; k--) {
         u64 s = k <= 9 ? D[k] : 0;
@@ -127,7 +146,7 @@ VG_HD void fe_mul_columns_(fe &r, const fe &a, const fe &b, const fe *c3) {
             D[k] = s;
         }
     }
-    if (c3) {   // 2^31 per limb against 2^63.76: no effect on the bounds; a mad, not mov + 64-bit add
+    if (!LEAN && c3) {   // 2^31 per limb against 2^63.76: no effect on the bounds; a mad, not mov + 64-bit add
         const u32 one = fe_opaque_<1>();
 #pragma unroll
         for (int k = 0; k < 9; k++) D[k] += (u64)c3->n[k] * one;
@@ -172,13 +191,15 @@ VG_HD void fe_sqr(fe &r, const fe &a) {
 
 // r = a * b + c, c of magnitude <= 3: c's limbs join the low product digits before the fold, so the
 // sum costs nine 32-bit adds and no extra carry pass.  Result magnitude 1 (as fe_mul).
+template <bool LEAN = false>
 VG_HD void fe_mul_add(fe &r, const fe &a, const fe &b, const fe &c3) {
-    fe_mul_columns_<false>(r, a, b, &c3);
+    fe_mul_columns_<false, LEAN>(r, a, b, &c3);
 }
 
 // r = a^2 + c, c of magnitude <= 3 (see fe_mul_add); a of magnitude 1.
+template <bool LEAN = false>
 VG_HD void fe_sqr_add(fe &r, const fe &a, const fe &c3) {
-    fe_mul_columns_<true>(r, a, a, &c3);
+    fe_mul_columns_<true, LEAN>(r, a, a, &c3);
 }
 
 // Canonical representative of a WEAKLY NORMALISED value (magnitude 1: output of fe_mul / fe_sqr / fe_*_add /

@@ -288,6 +288,28 @@ __global__ void __launch_bounds__(64) seq_inv_kernel(u32 *root, u32 groups) {
 
 // ---- stage 3: walk the tree down, finish the additions, hash, filter ---------------------------------------
 
+// Down-sweep of a workgroup's product tree in LDS (node 1 holds root^-1 on entry): inv[c] = inv[c >> 1] * node[c ^ 1].
+// One CHILD per lane: a level of `width` parents occupies 2 * width lanes with one product each, so wave 0 runs one
+// multiplication per level — seven in a row, eight wave-multiplications per workgroup — where one parent per lane with both
+// of its children ran two in a row per level (fourteen) while the other three waves of the workgroup stood at the barrier.
+// A child's lane overwrites the node its sibling's lane reads: the two are neighbouring lanes of ONE wave (c and c ^ 1, tid
+// and tid ^ 1), and every limb a lane stores depends on every limb it loaded, so both have read before either writes.
+__device__ __forceinline__ void tree_down_sweep(u32 *tree, int tid) {
+    static_assert(WG % 64 == 0 && WG >= 128, "siblings c and c ^ 1 must be lanes of one 64-lane wave at every level");
+    for (int width = 1; width <= WG / 4; width <<= 1) {
+        if (tid < 2 * width) {
+            const int c = 2 * width + tid;
+            fe ik, sib, ic;
+            lds_load_fe(tree, WG, c >> 1, ik);
+            lds_load_fe(tree, WG, c ^ 1, sib);
+            fe_mul(ic, ik, sib);
+            __builtin_amdgcn_wave_barrier();   // (no instruction: the stores stay behind the wave's loads in the schedule as well)
+            lds_store_fe(tree, WG, c, ic);
+        }
+        __syncthreads();
+    }
+}
+
 // FULL: the filter is the pattern's whole DFA (DEVF_DFA): its tables are staged into dynamic LDS and every
 // key's address is encoded and matched on the device (core/dfa_eval.h).  A separate instantiation so
 // that the extra registers of the Base58Check path do not touch the prefilter kernels' occupancy.
@@ -377,6 +399,10 @@ seq_bwd_kernel(const SeqArgs args) {
     // SHA-256 block's sixteen message words; the six-image on-device matcher) keep the running inverse in 9 KB of LDS of its own instead
     constexpr bool PARKI = VG_PARKI && !PARK && !PARK2 && !LONE && (FMT == VGF_P2PKH_UNCOMPRESSED || vgf_is_eth(FMT) || (FMT == VGF_P2PKH && FULL && ENDO));
     __shared__ u32 rpark[PARK ? 17 * WG : (PARK2 || PARKI) ? 9 * WG : 1];   // (PARK: R.y's top limb stays in a register: 26 KB of LDS per workgroup lets six share a CU)
+    // LEANMUL: the two products with an addend take core/fe.h's LEAN form (18 fewer multiply-adds and 8 fewer half-rate shifts per key).  The
+    // compressed-key formats only: the others (and the six-image on-device matcher, which parks its running inverse in LDS to stay under it)
+    // sit at or near the 128-register ceiling with the order of instructions they have (profiles/r05_kernel_resources.txt).
+    constexpr bool LEANMUL = !(FULL && ENDO) && (FMT == VGF_P2PKH || FMT == VGF_P2WPKH || FMT == VGF_P2SH_P2WPKH);
     const int tid = threadIdx.x;
     const GenTables gtab{args.gtab, args.gtab16, args.gtab_bits};   // P2TR: fixed-window generator tables, read from global memory (L2 / Infinity Cache / HBM)
     u32 *dfa_lds = dyn_lds;
@@ -399,21 +425,7 @@ seq_bwd_kernel(const SeqArgs args) {
     __syncthreads();
     if (tid < 9) tree[tid * WG + 1] = args.root[(size_t)tid * args.groups + blockIdx.x];   // root^-1
     __syncthreads();
-    // down-sweep: inv[2k] = inv[k] * node[2k+1], inv[2k+1] = inv[k] * node[2k]
-    for (int width = 1; width <= WG / 4; width <<= 1) {
-        if (tid < width) {
-            const int k = width + tid;
-            fe ik, a, b, ia, ib;
-            lds_load_fe(tree, WG, k, ik);
-            lds_load_fe(tree, WG, 2 * k, a);
-            lds_load_fe(tree, WG, 2 * k + 1, b);
-            fe_mul(ia, ik, b);
-            fe_mul(ib, ik, a);
-            lds_store_fe(tree, WG, 2 * k, ia);
-            lds_store_fe(tree, WG, 2 * k + 1, ib);
-        }
-        __syncthreads();
-    }
+    tree_down_sweep(tree, tid);
     const u32 *pre = args.pre + u;
     fe inv;
     {
@@ -524,7 +536,7 @@ seq_bwd_kernel(const SeqArgs args) {
 #pragma unroll
             for (int i = 0; i < 9; i++) dy.n[i] += q.nqy[i];   // magnitude <= 3
             fe_mul(lam, dy, idx);
-            fe_sqr_add(x3, lam, nsum);            // lam^2 - R.x - Q.x, weakly normalised
+            fe_sqr_add<LEANMUL>(x3, lam, nsum);   // lam^2 - R.x - Q.x, weakly normalised
             // VG_EC_SPRIO (A/B): the carry chains between the multiplications are runs of full-rate instructions: at priority 0 they can ride
             // behind other waves' half-rate instructions like the hash blocks' full-rate runs do
             if (VG_EC_SPRIO && !LONE) __builtin_amdgcn_s_setprio(0);
@@ -533,7 +545,7 @@ seq_bwd_kernel(const SeqArgs args) {
 #pragma unroll
             for (int i = 0; i < 9; i++) t.n[i] += q.qx[i];                                  // magnitude 3
             if (VG_EC_SPRIO && !LONE) __builtin_amdgcn_s_setprio(VG_BASE_PRIO);
-            fe_mul_add(y3, lam, t, nqy);          // lam*(Q.x - x3) - Q.y
+            fe_mul_add<LEANMUL>(y3, lam, t, nqy); // lam*(Q.x - x3) - Q.y
             if (VG_EC_SPRIO && !LONE) __builtin_amdgcn_s_setprio(0);
             if (FMT == VGF_P2PKH || FMT == VGF_P2WPKH || FMT == VGF_P2SH_P2WPKH)
                 y3.n[0] = fe_parity_weak(y3);     // a compressed key takes only the parity of y (bit 0 is all that is read)
