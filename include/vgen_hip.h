@@ -102,6 +102,32 @@ typedef enum vgen_format {
  * k <= 5 (the last characters), alone or with ranges (a pattern anchored at both ends), 3 = match-all, 0 = neither end is usable:
  * every payload goes to the host (correct and slow).  The device test is a superset; the host confirms with the exact automaton. */
 #define VGEN_FMT_SOLANA 12u
+/* And one that WALKS on that curve: VGEN_FMT_ONION, 13 (not a format of the reference; 11 stays unassigned).  A Tor v3 onion service
+ * loads an EXPANDED secret key (hs_ed25519_secret_key: the scalar itself and a 32-byte nonce key), not a seed, so a, a + 8, a + 16, ...
+ * are all usable keys and A(a + 8 i) = A(a) + i (8B): a dispatch tests the scalars base + 8 (first_index + i) at a handful of field
+ * products per key.  The KEY of this format (vgen_generated.key; hex = wif = its 64 hex digits) is the scalar as 32 LITTLE-endian
+ * bytes - bytes 0..31 of Tor's expanded key; vgen_onion_expand appends the nonce key.  Payload: the 32 bytes of A as RFC 8032 encodes
+ * them, as for format 12; all zero in a dump slot whose scalar is 0 (no key) - vgen_address_from_payload is VGEN_E_UNSUPPORTED for
+ * that payload: as a key it would be y = 0, a point of order 4, which Tor refuses.  Address string: 56 lowercase Base32 characters (RFC
+ * 4648 alphabet a-z2-7, no padding) of A || checksum[2] || 0x03, checksum = SHA3-256(".onion checksum" || A || 0x03)[0..2]; the string
+ * does not include ".onion".  The last character is always 'd', the 55th one of a i q y; characters 0..48 depend on y alone.
+ * Entry points: vgen_create (VGEN_FLAG_ENDO: VGEN_E_UNSUPPORTED; no secp256k1 scratch or generator table - the walk's lane points and
+ * the shared Ed25519 table are counted in vgen_memory_info.table_bytes, the walk scratch of 36 B per key and frame in frames_bytes),
+ * vgen_dispatch_onion, vgen_wait, vgen_read_dump / vgen_dump_view (32 B per slot), vgen_set_filter, vgen_set_match_cap, the frame
+ * timers, vgen_address_from_payload, vgen_derive (key = the scalar), vgen_key_to_wif (hex), the pattern front end (charset "Base32";
+ * invalid characters 0 1 8 9 and, without case_insensitive, upper case; difficulty 32^k) and vgen_scan / vgen_scan_multi: batch b of
+ * shard s is vgen_dispatch_onion(vgen_onion_base(seed, s), b * batch_size); seed 0 = 24 bytes of OS entropy, a nonzero seed makes the
+ * keys guessable as for format 12; every candidate is re-derived on the host (scalar x B) before it is reported; a VGEN_E_RANGE of
+ * the dispatch (probability about 2^-187) ends the scan with that status.  THE KEYS OF ONE SCAN ARE NEIGHBOURS ON ONE WALK: whoever
+ * learns one secret key of a scan and the scan's other addresses can derive the others' secrets - keys handed to different parties
+ * come from different scans.
+ * VGEN_E_UNSUPPORTED with a message: vgen_dispatch, vgen_dispatch_keys, vgen_dispatch_random*, has_start / has_end, checkpoint_path,
+ * vgen_set_base_point and the split functions, vgen_filter_compile_list / vgen_scan_list, score specifications.
+ * Device filter kinds: 2 = masked bits over the eight payload words (start-anchored prefixes, classes and case-insensitivity
+ * included; bit 7 of byte 31, the sign of x, is never tested), 3 = match-all, 0 = everything else - suffixes, unanchored patterns,
+ * whatever touches characters >= 49 only: every payload goes to the host (correct and slow).  The device test is a superset; the host
+ * confirms with the exact automaton on the encoded address. */
+#define VGEN_FMT_ONION 13u
 
 /* Parameters of vgen_create; replaces the arguments of GpuRunner::new(batch_size, backend)
  * (src/gpu.rs:138) plus the buffer sizing it derives from them (src/gpu.rs:391-500). */
@@ -676,6 +702,22 @@ int vgen_solana_keypair_base58(const uint8_t seed[32], char *out, size_t cap);
 /* Strict: VGEN_E_INVALID for a character outside the Base58 alphabet or a value that is not exactly 32 bytes.  Curve membership
  * is not tested. */
 int vgen_solana_decode(const char *address, uint8_t pub[32]);
+
+/* ---- Tor v3 onion addresses (VGEN_FMT_ONION) ------------------------------------------------------------------------------------ */
+/* The 56-character address (no ".onion") of a public key; cap >= 57.  Returns the length. */
+int vgen_onion_encode(const uint8_t pub[32], char *out, size_t cap);
+/* Strict: VGEN_E_INVALID for a wrong length, upper or mixed case, a character outside a-z2-7, a version byte other than 3 or a
+ * bad checksum.  A trailing ".onion" is accepted.  Curve membership is not tested. */
+int vgen_onion_decode(const char *address, uint8_t pub[32]);
+/* The 64 bytes Tor's hs_ed25519_secret_key holds behind its 32-byte header: scalar_le || nonce key, the nonce key being
+ * SHA-512("vgen-mi355x onion nonce key" || scalar_le)[32..64] - a function of the scalar alone, different for every key of a walk. */
+int vgen_onion_expand(const uint8_t scalar_le[32], uint8_t out[64]);
+/* The base scalar of stream `stream` under `seed`: the clamped scalar (RFC 8032 5.1.5) of the Ed25519 seed vgen_solana_seed(seed,
+ * stream, 0) - in [2^254, 2^255) and a multiple of 8.  Little-endian. */
+int vgen_onion_base(const uint8_t seed[24], uint32_t stream, uint8_t scalar_le[32]);
+/* Candidate i of the dispatch has the scalar base + 8 (first_index + i).  VGEN_E_INVALID when base is no multiple of 8, VGEN_E_RANGE
+ * when base + 8 (first_index + batch_size - 1) >= 2^255; nothing is enqueued in either case. */
+int vgen_dispatch_onion(vgen_ctx *ctx, uint32_t frame, const uint8_t base_scalar_le[32], uint64_t first_index);
 
 #ifdef __cplusplus
 }

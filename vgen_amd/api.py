@@ -62,6 +62,9 @@ FORMAT_NOSTR = 10
 # VGEN_FMT_SOLANA: a Solana address, the Ed25519 public key of a 32-byte seed in Base58 (not in the reference).  The key of this format
 # is the SEED; 11 stays unassigned.  Scans of such a runner always draw independent seeds (ScanConfig.random_keys is implied).
 FORMAT_SOLANA = 12
+# VGEN_FMT_ONION: a Tor v3 onion address, the Ed25519 public key of a SCALAR in Base32 (not in the reference).  The key of this format is
+# the scalar as 32 little-endian bytes, and scans walk a + 8 i from the base scalar of their seed: the keys of one scan are neighbours.
+FORMAT_ONION = 13
 
 
 def _fmt(v):
@@ -168,6 +171,11 @@ _L.vgen_solana_seed.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint6
 _L.vgen_solana_public_key.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
 _L.vgen_solana_keypair_base58.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
 _L.vgen_solana_decode.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+_L.vgen_onion_encode.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
+_L.vgen_onion_decode.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+_L.vgen_onion_expand.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+_L.vgen_onion_base.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p]
+_L.vgen_dispatch_onion.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64]
 _L.vgen_create2_address.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
 _L.vgen_create2_salt.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_char_p]
 _L.vgen_set_create2.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p]
@@ -373,6 +381,53 @@ def solana_decode(address: str) -> Optional[bytes]:
     out = ctypes.create_string_buffer(32)
     if _L.vgen_solana_decode(address.encode(), out) != 0:
         return None
+    return out.raw
+
+
+def _scalar_le(scalar) -> bytes:
+    if isinstance(scalar, int):
+        return scalar.to_bytes(32, "little")
+    scalar = bytes.fromhex(scalar) if isinstance(scalar, str) else bytes(scalar)
+    if len(scalar) != 32:
+        raise ValueError("an Ed25519 scalar is 32 little-endian bytes")
+    return scalar
+
+
+def onion_address(pub) -> str:
+    """vgen_onion_encode: the 56-character Tor v3 address (without ".onion") of a 32-byte Ed25519 public key."""
+    pub = bytes.fromhex(pub) if isinstance(pub, str) else bytes(pub)
+    if len(pub) != 32:
+        raise ValueError("an Ed25519 public key is 32 bytes")
+    out = ctypes.create_string_buffer(64)
+    _check(_L.vgen_onion_encode(pub, out, 64))
+    return out.value.decode()
+
+
+def onion_decode(address: str) -> Optional[bytes]:
+    """vgen_onion_decode (strict) -> the 32 bytes of the public key, or None: wrong length, upper or mixed case, a character outside
+    a-z2-7, a version other than 3 or a bad checksum.  A trailing ".onion" is accepted."""
+    out = ctypes.create_string_buffer(32)
+    if _L.vgen_onion_decode(address.encode(), out) != 0:
+        return None
+    return out.raw
+
+
+def onion_expand(scalar) -> bytes:
+    """vgen_onion_expand: the 64 bytes of Tor's expanded secret key - the scalar (an int, or its 32 little-endian bytes) and a nonce
+    key derived from it."""
+    out = ctypes.create_string_buffer(64)
+    _check(_L.vgen_onion_expand(_scalar_le(scalar), out))
+    return out.raw
+
+
+def onion_base(seed, stream: int) -> bytes:
+    """vgen_onion_base: the base scalar (32 little-endian bytes) an onion scan's shard `stream` walks from.
+    seed: an integer < 2^64 (standing for its 8 little-endian bytes and sixteen zero bytes) or the 24 seed bytes."""
+    if not isinstance(seed, (bytes, bytearray)):
+        seed = int(seed).to_bytes(8, "little") + bytes(16)
+    assert len(seed) == 24
+    out = ctypes.create_string_buffer(32)
+    _check(_L.vgen_onion_base(bytes(seed), stream, out))
     return out.raw
 
 
@@ -719,7 +774,7 @@ class GpuRunner:
         b, f, m = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         _L.vgen_get_info(h, ctypes.byref(b), ctypes.byref(f), ctypes.byref(m))
         self.batch_size, self.frames, self.match_cap, self.format = b.value, f.value, m.value, _fmt(fmt)
-        self.payload_bytes = 32 if int(self.format) in (int(AddressFormat.P2tr), FORMAT_NOSTR, FORMAT_SOLANA) else 20
+        self.payload_bytes = 32 if int(self.format) in (int(AddressFormat.P2tr), FORMAT_NOSTR, FORMAT_SOLANA, FORMAT_ONION) else 20
         self._pattern = None
 
     def topology(self) -> dict:
@@ -790,6 +845,12 @@ class GpuRunner:
     def set_create3(self, job: "Create3Job"):
         """vgen_set_create3: a CREATE3 job on an EthereumCreate2 runner; dispatch_create2 then tests its salts."""
         _check(_L.vgen_set_create3(self._h, job.factory, job.proxy_init_code_hash, job.salt_prefix, job.guard, job.guard_len), self._h)
+
+    def dispatch_onion(self, base_scalar, first_index: int, frame: int):
+        """vgen_dispatch_onion: candidate i has the Ed25519 scalar base + 8 * (first_index + i); base_scalar an int or its 32
+        little-endian bytes, a multiple of 8.  Results as for dispatch()."""
+        self._n_keys = self.batch_size
+        _check(_L.vgen_dispatch_onion(self._h, frame, _scalar_le(base_scalar), first_index), self._h)
 
     def dispatch_create2(self, first_counter: int, frame: int):
         """vgen_dispatch_create2: salts first_counter .. first_counter + batch_size - 1 of the job; results as for dispatch()."""

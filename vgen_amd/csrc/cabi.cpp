@@ -8,6 +8,7 @@
 
 #include "../../include/vgen_hip.h"
 #include "host/ed_host.h"
+#include "host/onion_host.h"
 #include "host/encode.h"
 #include "host/filter.h"
 #include "host/pattern_info.h"
@@ -112,6 +113,10 @@ int vgen_filter_compile_list(const char *patterns, int case_insensitive, uint32_
     if (!patterns || !out) return VGEN_E_INVALID;
     if (format == vg::VGF_SOLANA) {
         g_last_error = "pattern lists are not provided for the solana format (12): a list's table holds intervals of 64 payload bits, Base58 of 32 bytes needs all 256";
+        return VGEN_E_UNSUPPORTED;
+    }
+    if (format == vg::VGF_ONION) {
+        g_last_error = "pattern lists are not provided for the onion format (13)";
         return VGEN_E_UNSUPPORTED;
     }
     vgen_filter *f = new vgen_filter();
@@ -240,13 +245,20 @@ int vgen_score(const vgen_filter *f, const char *address, uint32_t *score) {
     return vg::score_of(*f, address, nullptr, score, nullptr) ? VGEN_OK : VGEN_E_INVALID;
 }
 
+// An onion context walks Ed25519 scalars in steps of 8 from a base: the secp256k1 dispatches refuse it.
+static int refuse_onion(vgen_ctx *c, const char *what) {
+    return c->fail(VGEN_E_UNSUPPORTED, std::string(what) + ": an onion context walks Ed25519 scalars a + 8 i - use vgen_dispatch_onion");
+}
+
 int vgen_dispatch(vgen_ctx *ctx, uint32_t frame, const uint8_t start_key_be[32]) {
     if (!ctx) return VGEN_E_INVALID;
+    if (ctx->format == vg::VGF_ONION) return refuse_onion(ctx, "vgen_dispatch");
     return vg::rt_dispatch(ctx, frame, start_key_be);
 }
 
 int vgen_dispatch_keys(vgen_ctx *ctx, uint32_t frame, const uint8_t *keys_be, uint32_t n) {
     if (!ctx) return VGEN_E_INVALID;
+    if (ctx->format == vg::VGF_ONION) return refuse_onion(ctx, "vgen_dispatch_keys");
     return vg::rt_dispatch_keys(ctx, frame, keys_be, n);
 }
 
@@ -261,11 +273,13 @@ extern "C" int vgen_debug_fail_after(vgen_ctx *ctx, uint64_t after_dispatches) {
 
 int vgen_dispatch_random(vgen_ctx *ctx, uint32_t frame, uint64_t seed, uint32_t stream, uint64_t first_index) {
     if (!ctx) return VGEN_E_INVALID;
+    if (ctx->format == vg::VGF_ONION) return refuse_onion(ctx, "vgen_dispatch_random");
     return vg::rt_dispatch_random(ctx, frame, vg::rnd_seed_from_u64(seed), stream, first_index);
 }
 
 int vgen_dispatch_random_seed(vgen_ctx *ctx, uint32_t frame, const uint8_t seed[24], uint32_t stream, uint64_t first_index) {
     if (!ctx || !seed) return VGEN_E_INVALID;
+    if (ctx->format == vg::VGF_ONION) return refuse_onion(ctx, "vgen_dispatch_random_seed");
     return vg::rt_dispatch_random(ctx, frame, vg::rnd_seed_from_bytes(seed), stream, first_index);
 }
 
@@ -330,6 +344,7 @@ int vgen_address_from_payload(uint32_t format, const uint8_t *payload, char *out
 int vgen_key_to_wif(uint32_t format, const uint8_t key_be[32], char *out, size_t cap) {
     if (!key_be) return VGEN_E_INVALID;
     if (format == vg::VGF_SOLANA) return copy_out(vg::key_to_wif(format, key_be), out, cap);   // a seed: any 32 bytes
+    if (format == vg::VGF_ONION) return copy_out(vg::key_to_wif(format, key_be), out, cap);    // an Ed25519 scalar, little-endian
     vg::Scalar k;
     vg::scalar_from_be(k, key_be);
     if (!vg::scalar_is_valid(k)) return VGEN_E_RANGE;
@@ -484,6 +499,8 @@ int vgen_set_base_point(vgen_ctx *ctx, const uint8_t *pub, size_t len) {
         return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: an ethereum-create2 context tests salts - there is no key to split");
     if (ctx->format == vg::VGF_SOLANA)
         return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: a solana key is a seed whose scalar is its hash - partial keys cannot be added");
+    if (ctx->format == vg::VGF_ONION)
+        return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: split keys are not provided for the onion format");
     if (!ctx->base_set) return ctx->fail(VGEN_E_UNSUPPORTED, "vgen_set_base_point: this runtime does not serve split-key dispatches");
     const bool clear = !pub && len == 0;
     vg::ge pt;
@@ -510,7 +527,7 @@ int vgen_split_dropped(const vgen_ctx *ctx, uint64_t *n) {
 
 int vgen_split_derive(uint32_t format, const uint8_t *pub, size_t len, const uint8_t partial_be[32], uint32_t variant, char *address, size_t cap) {
     if (!pub || !partial_be || !address) return VGEN_E_INVALID;
-    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2 || format == vg::VGF_SOLANA) return VGEN_E_UNSUPPORTED;
+    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2 || vg::vgf_is_ed((int)format)) return VGEN_E_UNSUPPORTED;
     vg::ge base, pt, img;
     if (variant >= vg::vgf_endo_images((int)format) || !vg::point_from_sec1(pub, len, base)) return VGEN_E_INVALID;
     vg::Scalar k;
@@ -526,7 +543,7 @@ int vgen_split_derive(uint32_t format, const uint8_t *pub, size_t len, const uin
 int vgen_split_combine(uint32_t format, const uint8_t secret_be[32], const uint8_t partial_be[32], const char *address, uint8_t final_be[32],
                        uint32_t *variant) {
     if (!secret_be || !partial_be || !address || !final_be) return VGEN_E_INVALID;
-    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2 || format == vg::VGF_SOLANA) return VGEN_E_UNSUPPORTED;
+    if (!vg::format_charset_name(format) || format == vg::VGF_ETHEREUM_CREATE2 || vg::vgf_is_ed((int)format)) return VGEN_E_UNSUPPORTED;
     vg::Scalar s, k, sum;
     vg::scalar_from_be(s, secret_be);
     vg::scalar_from_be(k, partial_be);
@@ -591,6 +608,35 @@ int vgen_solana_keypair_base58(const uint8_t seed[32], char *out, size_t cap) {
 int vgen_solana_decode(const char *address, uint8_t pub[32]) {
     if (!address || !pub) return VGEN_E_INVALID;
     return vg::solana_decode(address, pub) ? VGEN_OK : VGEN_E_INVALID;
+}
+
+// ---- Tor v3 onion addresses ----
+
+int vgen_onion_encode(const uint8_t pub[32], char *out, size_t cap) {
+    if (!pub || !out) return VGEN_E_INVALID;
+    return copy_out(vg::onion_encode(pub), out, cap);
+}
+
+int vgen_onion_decode(const char *address, uint8_t pub[32]) {
+    if (!address || !pub) return VGEN_E_INVALID;
+    return vg::onion_decode(address, pub) ? VGEN_OK : VGEN_E_INVALID;
+}
+
+int vgen_onion_expand(const uint8_t scalar_le[32], uint8_t out[64]) {
+    if (!scalar_le || !out) return VGEN_E_INVALID;
+    vg::onion_expand(scalar_le, out);
+    return VGEN_OK;
+}
+
+int vgen_onion_base(const uint8_t seed[24], uint32_t stream, uint8_t scalar_le[32]) {
+    if (!seed || !scalar_le) return VGEN_E_INVALID;
+    vg::onion_base(vg::rnd_seed_from_bytes(seed), stream, scalar_le);
+    return VGEN_OK;
+}
+
+int vgen_dispatch_onion(vgen_ctx *ctx, uint32_t frame, const uint8_t base_scalar_le[32], uint64_t first_index) {
+    if (!ctx) return VGEN_E_INVALID;
+    return vg::rt_dispatch_onion(ctx, frame, base_scalar_le, first_index);
 }
 
 }  // extern "C"

@@ -57,6 +57,7 @@ struct Opts {
     // split-key search: --base-pubkey (generate), and the requester's `combine`
     std::string base_pubkey, secret_file, partial;
     std::string keypair_dir;                  // -f solana: one <address>.json per result, the 64-number array solana-keygen reads
+    std::string key_dir;                      // -f onion: one directory <address>.onion per result, the three files Tor reads (mkp224o's layout)
     bool has_base = false;
     bool create3() const { return format == "ethereum-create3"; }
     bool any_create3_option() const { return has_proxy_hash || has_salt_guard || salt_guard_hash; }
@@ -80,7 +81,8 @@ int format_id(const std::string &f) {
     if (f == "p2pkh-uncompressed") return VGEN_FMT_P2PKH_UNCOMPRESSED;
     if (f == "nostr") return VGEN_FMT_NOSTR;
     if (f == "solana") return VGEN_FMT_SOLANA;
-    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2, ethereum-create3, nostr, solana)");
+    if (f == "onion") return VGEN_FMT_ONION;
+    die("invalid value '" + f + "' for '--format' (p2pkh, p2wpkh, p2sh-p2wpkh, p2tr, ethereum, ethereum-contract, ethereum-create2, ethereum-create3, nostr, solana, onion)");
 }
 
 const char *format_display(int id) {   // Display for AddressFormat, src/address.rs:48-58
@@ -94,6 +96,7 @@ const char *format_display(int id) {   // Display for AddressFormat, src/address
     case VGEN_FMT_ETHEREUM_CREATE2: return "Ethereum contract (CREATE2)";
     case VGEN_FMT_NOSTR: return "Nostr (npub)";
     case VGEN_FMT_SOLANA: return "Solana";
+    case VGEN_FMT_ONION: return "Tor v3 onion";
     default: return "Ethereum";
     }
 }
@@ -213,7 +216,7 @@ void usage() {
             "          contract the key's account creates with its FIRST transaction, nonce 0; results carry that account as `deployer`),\n"
             "          nostr (the Nostr public key npub1... of NIP-19: Bech32 of the BIP-340 x-only key; results carry the nsec1... secret key\n"
             "          as `wif` and the key's 32 bytes as `public_key_hex`; unseeded searches test three keys per curve point),\n"
-            "          solana (see below)\n"
+            "          solana, onion (see below)\n"
             "  vgen-hip generate -p PATTERN [-f FORMAT] [-i] [-c COUNT] [-o text|json|jsonl|csv|minimal] [--file PATH]\n"
             "                    [--gpu-batch-size N] [--repeat N] [-q] [--seed S] [--devices 0,1,..|all] [--frames F]\n"
             "                    [--frames F]          (dispatches in flight, default 12; several searches on ONE device share it\n"
@@ -256,6 +259,13 @@ void usage() {
             "                    and --no-endo are accepted and change nothing).  Results carry the seed in hex and the keypair string wallets\n"
             "                    import; --keypair-dir writes DIR/<address>.json, the 64-number array solana-keygen reads, mode 0600.  --seed makes\n"
             "                    the keys guessable.  estimate takes the format; range, --checkpoint, --patterns-file and --base-pubkey do not)\n"
+            "  vgen-hip generate -f onion -p PATTERN [-i] [-c COUNT] [-o ..] [--devices ..] [--seed S] [--key-dir DIR]   (Tor v3 onion addresses:\n"
+            "                    56 Base32 characters a-z2-7, printed with .onion.  The key is the Ed25519 SCALAR and the search walks a, a + 8,\n"
+            "                    a + 16, ...: THE KEYS OF ONE RUN ARE NEIGHBOURS - whoever learns one of them and the run's other addresses can\n"
+            "                    derive the others, so keys for different parties come from different runs.  Results carry the 64-byte expanded\n"
+            "                    secret key in hex; --key-dir writes DIR/<address>.onion/ with hs_ed25519_secret_key, hs_ed25519_public_key and\n"
+            "                    hostname, modes 0700 / 0600.  --random-keys and --no-endo are accepted and change nothing; --seed makes the keys\n"
+            "                    guessable.  estimate takes the format; range, --checkpoint, --patterns-file, --base-pubkey and verify do not)\n"
             "  vgen-hip generate --patterns-file FILE [--per-pattern N] ...   (instead of -p: one start-anchored prefix per line,\n"
             "                    one scan; N results per pattern (default 1, 0 = unbounded), -c caps the total (default: none);\n"
             "                    each result's pattern field is the lowest-index line it satisfies.  range takes it too)\n"
@@ -280,7 +290,7 @@ Opts parse(int argc, char **argv) {
                                                   "--seed", "--devices", "--frames", "--checkpoint", "--range", "--puzzle", "--key", "--address",
                                                   "--prefix-length", "--provider-table", "--threads", "--backend", "--cpu-batch-size", "--table-bits-max",
                                                   "--mem-budget-gib", "--patterns-file", "--per-pattern", "--deployer", "--init-code-hash", "--init-code-file",
-                                                  "--salt-prefix", "--salt-start", "--proxy-init-code-hash", "--salt-guard", "--base-pubkey", "--secret-file", "--partial", "--keypair-dir"};
+                                                  "--salt-prefix", "--salt-start", "--proxy-init-code-hash", "--salt-guard", "--base-pubkey", "--secret-file", "--partial", "--keypair-dir", "--key-dir"};
     static const char short_with_value[] = "pfcorkaltT";
     std::vector<std::string> args;
     bool next_is_value = false;
@@ -363,6 +373,7 @@ Opts parse(int argc, char **argv) {
         else if (a == "--secret-file") o.secret_file = val();
         else if (a == "--partial") o.partial = val();
         else if (a == "--keypair-dir") o.keypair_dir = val();
+        else if (a == "--key-dir") o.key_dir = val();
         else if (a == "-t" || a == "--threads" || a == "--backend" || a == "--cpu-batch-size") (void)val();   // accepted, not applicable
         else if (a == "-h" || a == "--help") { usage(); exit(0); }
         else die("unexpected argument '" + a + "'");
@@ -665,6 +676,23 @@ void write_keypair_file(const std::string &dir, const vgen_generated &g) {
     if (close(fd) != 0 || !ok) die("cannot write keypair file '" + path + "'");
 }
 
+// -f onion --key-dir: DIR/<address>.onion/ (mode 0700) with the three files of a Tor hidden-service directory, mode 0600 - mkp224o's layout.
+void write_onion_dir(const std::string &dir, const vgen_generated &g, const uint8_t expanded[64], const uint8_t pub[32]) {
+    const std::string d = dir + "/" + g.address + ".onion";
+    if (mkdir(d.c_str(), 0700) != 0 && errno != EEXIST) die("cannot create key directory '" + d + "'");
+    if (chmod(d.c_str(), 0700) != 0) die("cannot set the mode of key directory '" + d + "'");
+    auto put = [&](const char *name, const std::string &body) {
+        const std::string path = d + "/" + name;
+        const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0600);
+        if (fd < 0 || fchmod(fd, 0600) != 0) die("cannot write key file '" + path + "'");
+        const bool ok = write(fd, body.data(), body.size()) == (ssize_t)body.size();
+        if (close(fd) != 0 || !ok) die("cannot write key file '" + path + "'");
+    };
+    put("hs_ed25519_secret_key", std::string("== ed25519v1-secret: type0 ==") + std::string(3, '\0') + std::string((const char *)expanded, 64));
+    put("hs_ed25519_public_key", std::string("== ed25519v1-public: type0 ==") + std::string(3, '\0') + std::string((const char *)pub, 32));
+    put("hostname", std::string(g.address) + ".onion\n");
+}
+
 std::string list_pattern_of(const vgen_filter *list, const char *address) {
     uint32_t idx = 0, n = 0;
     if (vgen_filter_which(list, address, &idx, 1, &n) != VGEN_OK || n == 0) return std::string();
@@ -690,6 +718,13 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         if (list) die("the argument '--patterns-file' cannot be used with '-f solana': pattern lists are not provided for this format");
         if (o.has_base) die("the argument '--base-pubkey' cannot be used with '-f solana': a seed cannot be split");
     } else if (!o.keypair_dir.empty()) die("the argument '--keypair-dir' belongs to '-f solana'");
+    const bool onion = fmt == VGEN_FMT_ONION;
+    if (onion) {   // the walk starts at the base scalar of the run's seed: no range, nothing resumes, no lists, nothing splits
+        if (has_range) die("'-f onion' cannot be used with 'range': an onion search walks from the base scalar of its seed - there is no key range");
+        if (!o.checkpoint.empty()) die("the argument '--checkpoint' cannot be used with '-f onion': checkpoints are not provided for this format");
+        if (list) die("the argument '--patterns-file' cannot be used with '-f onion': pattern lists are not provided for this format");
+        if (o.has_base) die("the argument '--base-pubkey' cannot be used with '-f onion': split keys are not provided for this format");
+    } else if (!o.key_dir.empty()) die("the argument '--key-dir' belongs to '-f onion'");
     Create2Job job;
     Create3Job job3;
     if (create3) job3 = create3_job(o, has_range, list != nullptr);
@@ -731,7 +766,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         // a vanity search proper — random base, no range, no seed, no checkpoint — may test any keys it likes:
         // six images per curve point (VGEN_FLAG_ENDO, +30 % keys per second); everything else walks k0 + i
         // (--random-keys: six keys per draw; seeds name candidate streams there, so they do not rule it out)
-        if (!o.no_endo && fmt != 3 && !create2 && !solana && (o.random_keys || (!has_range && !o.seed && o.checkpoint.empty()))) p.flags |= VGEN_FLAG_ENDO;
+        if (!o.no_endo && fmt != 3 && !create2 && !solana && !onion && (o.random_keys || (!has_range && !o.seed && o.checkpoint.empty()))) p.flags |= VGEN_FLAG_ENDO;
         vgen_ctx *c = nullptr;
         if (vgen_create(&p, &c) != VGEN_OK) die(std::string("GPU initialization failed: ") + vgen_last_error(nullptr));
         if (o.has_base && vgen_set_base_point(c, base_pub, (size_t)base_len) != VGEN_OK) die(vgen_last_error(c));
@@ -872,6 +907,22 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         }
         // nostr: the address is the Bech32 of the x-only public key; its 32 bytes in hex beside it
         std::string pub_hex;
+        // onion: the key is the scalar; what Tor loads are the 64 expanded bytes, the address's 32 bytes are the public key
+        std::string expanded_hex;
+        if (onion) {
+            uint8_t ex[64], pub[32];
+            if (vgen_onion_expand(g.key, ex) != VGEN_OK || vgen_onion_decode(g.address, pub) != VGEN_OK) die("a result of an onion search is no address");
+            static const char HX[] = "0123456789abcdef";
+            for (int i = 0; i < 64; i++) {
+                expanded_hex.push_back(HX[ex[i] >> 4]);
+                expanded_hex.push_back(HX[ex[i] & 15]);
+            }
+            for (int i = 0; i < 32; i++) {
+                pub_hex.push_back(HX[pub[i] >> 4]);
+                pub_hex.push_back(HX[pub[i] & 15]);
+            }
+            if (!o.key_dir.empty()) write_onion_dir(o.key_dir, g, ex, pub);
+        }
         if (solana) {
             uint8_t pub[32];
             if (vgen_solana_decode(g.address, pub) != VGEN_OK) die("a result of a solana search is no address");
@@ -896,6 +947,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
         if (o.output == "text") {
             fprintf(w, "=== Match %zu of %zu ===\n", idx + 1, all.size());
             if (create2) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSalt    : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex);
+            else if (onion) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s.onion\nSecret key : %s\nPubkey  : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, expanded_hex.c_str(), pub_hex.c_str());
             else if (solana) fprintf(w, "Pattern : %s\nFormat  : %s\nAddress : %s\nSeed    : %s\nKeypair : %s\n", pattern.c_str(), fmt_name.c_str(), g.address, g.hex, keypair.c_str());
             else if (o.has_base) {
                 // a partial key: no key to anything without the secret behind the base public key (vgen-hip combine)
@@ -930,6 +982,7 @@ int run_search(const Opts &o, const std::string &pattern_arg, bool has_range, co
             if (!pub_hex.empty()) fprintf(w, "%s\"public_key_hex\":%s%s,", nl, sp, json_str(pub_hex).c_str());
             // split-key search: the partial key, the base it belongs to and the image - and no wif: a partial key is not importable
             if (solana) fprintf(w, "%s\"seed_hex\":%s%s,%s\"keypair_base58\":%s%s,", nl, sp, json_str(g.hex).c_str(), nl, sp, json_str(keypair).c_str());   // (no wif)
+            else if (onion) fprintf(w, "%s\"secret_key_hex\":%s%s,", nl, sp, json_str(expanded_hex).c_str());   // (the 64 expanded bytes; no wif)
             else if (o.has_base) fprintf(w, "%s\"partial_key_hex\":%s%s,%s\"base_public_key\":%s%s,%s\"variant\":%s%d,", nl, sp, json_str(g.hex + 2).c_str(), nl, sp,
                                     json_str(base_hex).c_str(), nl, sp, variant);
             else fprintf(w, "%s\"wif\":%s%s,%s\"private_key_hex\":%s%s,", nl, sp, json_str(g.wif).c_str(), nl, sp, json_str(g.hex).c_str());
@@ -980,6 +1033,13 @@ int main(int argc, char **argv) {
         if (!o.checkpoint.empty()) die("the argument '--checkpoint' cannot be used with '-f solana': checkpoints are not provided for this format");
         if (o.has_base) die("the argument '--base-pubkey' cannot be used with '-f solana': a seed cannot be split");
     }
+    if ((o.cmd == "generate" || o.cmd == "range") && o.format == "onion") {
+        if (o.cmd == "range") die("'-f onion' cannot be used with 'range': an onion search walks from the base scalar of its seed - there is no key range");
+        if (o.has_patterns_file) die("the argument '--patterns-file' cannot be used with '-f onion': pattern lists are not provided for this format");
+        if (!o.checkpoint.empty()) die("the argument '--checkpoint' cannot be used with '-f onion': checkpoints are not provided for this format");
+        if (o.has_base) die("the argument '--base-pubkey' cannot be used with '-f onion': split keys are not provided for this format");
+    }
+    if (o.cmd == "verify" && o.format == "onion") die("'-f onion' cannot be used with 'verify': the reference has no such format to verify against");
     if ((o.cmd == "generate" || o.cmd == "range") && o.has_patterns_file) {
         if (o.has_pattern) die("the argument '--patterns-file' cannot be used with '--pattern'");
         vgen_filter *list = load_pattern_list(o, format_id(o.format));

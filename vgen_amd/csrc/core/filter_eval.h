@@ -241,4 +241,28 @@ VG_HD bool filter_eval_sol(const DevFilter *f, const u32 *payload) {
     return hit;
 }
 
+// ---- Tor v3 onion addresses: Base32 of the 32-byte public key || checksum[2] || version ----
+// A function of its own, as above.  Character c of the address is bits 5c .. 5c + 4 of the byte stream, the first byte's top bit
+// first: characters 0 .. 48 are bits of y alone, so a start-anchored prefix is a masked test of the payload's big-endian words
+// (kind 2; kind 3 accepts all).  Bit 7 of byte 31 - the sign of x, which the walk's filter form does not compute - is masked out of
+// the payload before the compare: a superset, and no mask the compiler makes reaches that bit.
+VG_HD bool filter_eval_onion(const DevFilter *f, const u32 *payload) {
+    const u32 kind = f->kind;
+    if (kind != DEVF_MASKED) return kind != DEVF_RANGES;   // (ALL; HOST_ALL is judged elsewhere)
+    u32 H[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) H[i] = bswap32(payload[i]);
+    H[7] &= ~0x80u;
+    const u32 n = f->count;
+    bool hit = false;
+    for (u32 t = 0; t < n; t++) {
+        const DevFilterTest &T = f->tests[t];
+        u32 diff = 0;
+#pragma unroll
+        for (int i = 0; i < 8; i++) diff |= (H[i] & T.a[i]) ^ T.b[i];
+        hit = hit || (diff == 0);
+    }
+    return hit;
+}
+
 }  // namespace vg

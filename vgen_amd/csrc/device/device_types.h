@@ -21,6 +21,12 @@ constexpr int VGF_NOSTR{10};
 // Solana address: the Ed25519 public key of a 32-byte seed, 32 bytes, Base58 without checksum (not a format of the reference).  Format
 // 12; 11 stays unassigned like 8 and 9.  The only format on another curve: its key is the SEED, its kernels are ed_keys_kernel.
 constexpr int VGF_SOLANA{12};
+// Tor v3 onion address: the Ed25519 public key of a SCALAR (Tor loads an expanded secret key, not a seed), 32 bytes, Base32 with a
+// SHA3-256 checksum and a version byte (not a format of the reference).  Format 13.  The scalars a, a + 8, a + 16, ... are all keys, so
+// this format walks: onion_fwd_kernel / onion_bwd_kernel.
+constexpr int VGF_ONION{13};
+// the formats on the Ed25519 curve: no secp256k1 scratch, offset table or generator table
+constexpr bool vgf_is_ed(int fmt) { return fmt == VGF_SOLANA || fmt == VGF_ONION; }
 
 // the two formats whose payload is (derived from) the Ethereum account address: hex strings, both coordinates hashed
 constexpr bool vgf_is_eth(int fmt) { return fmt == VGF_ETHEREUM || fmt == VGF_ETHEREUM_CONTRACT; }
@@ -30,7 +36,7 @@ constexpr int vgf_string_format(int fmt) { return (fmt == VGF_ETHEREUM_CONTRACT 
 // point and stays what it is: a CREATE2 address has no point behind it)
 constexpr bool vgf_is_hex(int fmt) { return vgf_string_format(fmt) == VGF_ETHEREUM; }
 // payload words of a format: the 32-byte x-only keys (the taproot output key, the Nostr public key) take eight, everything else five
-constexpr int vgf_payload_words(int fmt) { return (fmt == VGF_P2TR || fmt == VGF_NOSTR || fmt == VGF_SOLANA) ? 8 : 5; }
+constexpr int vgf_payload_words(int fmt) { return (fmt == VGF_P2TR || fmt == VGF_NOSTR || fmt == VGF_SOLANA || fmt == VGF_ONION) ? 8 : 5; }
 // keys tested per curve point on a VGEN_FLAG_ENDO context: the six endomorphism / negation images, or - x-only keys, where (x, y)
 // and (x, -y) are one key - the three images x, beta x, beta^2 x
 constexpr uint32_t vgf_endo_images(int fmt) { return fmt == VGF_NOSTR ? 3u : 6u; }
@@ -316,6 +322,42 @@ struct EdArgs {
     uint32_t *payloads;          // slot i at payloads + 8 i: every slot (DUMP; zero where there is no key) or the slots of hit lanes only
     unsigned long long *hits;    // PRE: the hit mask, one bit per slot (batch / 64 words)
     const DevFilter *filter;     // PRE: the context's prefilter (kinds 1, 3, 7)
+};
+
+// ---- Tor v3 onion addresses (VGF_ONION; appended: no structure above changes) ----------------------------------------------------
+// The walk: candidate i of a dispatch has the scalar base + 8 (first + i), its point is A(base + 8 first) + i (8B).  With L = batch /
+// (2 ONION_S) lanes, lane u owns the affine table point R_u = (u S + S/2) (8B) and the dispatch shares the S points
+// U_j = (base + 8 (first + L S - S/2 + j)) B; the 2 S keys of a lane are
+//     U_j + R_u  at slot  L S + u S + j          U_j - R_u  at slot  L S - (u + 1) S + j,         j = 0 .. S - 1
+// which together tile 0 .. batch - 1.  S = 32: a lane's S slots of either sign are one aligned 32-bit word of the hit mask.
+constexpr int ONION_S = 32;
+constexpr int ONION_WG = 512;                // lanes per workgroup: its waves share one field inversion, as ED_WG
+constexpr int ONION_PT_WORDS = 27;           // x[9] y[9] t[9], canonical limbs
+constexpr uint32_t ONION_NO_SLOT = 0xFFFFFFFFu;
+// onion_points_kernel: point i = (start + i * step) B for i < n, with t = x y, or d x y when mul_d (the shared points).  Word w of
+// point i goes to out[w * wstride + i * istride]: (L, 1) for the lane table - coalesced across lanes -, (1, ONION_PT_WORDS) for the
+// shared points, which every lane reads at the same address.
+struct OnionPointsArgs {
+    const uint32_t *table;       // core/ed25519.h: ED_TABLE_WORDS words
+    uint32_t start[8];           // little-endian words
+    uint32_t step;
+    uint32_t n;
+    uint32_t mul_d;
+    uint32_t wstride, istride;
+    uint32_t *out;               // ONION_PT_WORDS x n words
+};
+// onion_fwd_kernel / onion_bwd_kernel.  Scratch of a frame: pre = 2 S x 9 x L words (prefix product before element e of lane g, word
+// w, at [(e * 9 + w) * L + g]; element 2 j is 1 - k_j, element 2 j + 1 is 1 + k_j), then inv = 9 x L words (1 / the lane's product).
+struct OnionArgs {
+    const uint32_t *uni;         // the dispatch's S shared points: ONION_PT_WORDS x S words, [j * ONION_PT_WORDS + w]
+    const uint32_t *lane;        // the context's lane points: ONION_PT_WORDS x L words, [w * L + u]
+    uint32_t *pre;
+    uint32_t *inv;
+    uint32_t lanes;              // L
+    uint32_t zero_slot;          // the slot whose scalar is 0 (no key: its payload is zero and it never hits), or ONION_NO_SLOT
+    uint32_t *payloads;          // slot i at payloads + 8 i: every slot (dump) or the slots of hit lanes only
+    uint32_t *hits;              // filter form: the hit mask as 32-bit words (bit s & 31 of word s >> 5), batch / 32 words
+    const DevFilter *filter;     // filter form: the context's prefilter (kinds 2 and 3)
 };
 
 }  // namespace vg

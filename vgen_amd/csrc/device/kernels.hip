@@ -50,6 +50,7 @@
 #include "../core/dfa_eval.h"
 #include "../core/ec.h"
 #include "../core/ed25519.h"
+#include "../core/ed_walk.h"
 #include "../core/filter_eval.h"
 #include "../core/hash.h"
 #include "../core/rnd.h"
@@ -2558,6 +2559,221 @@ hipError_t launch_ed_keys(const EdArgs &a, uint32_t batch, const PtabArgs *compa
     hipLaunchKernelGGL((ed_keys_kernel<true>), dim3(batch / ED_WG), dim3(ED_WG), 0, stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ptab_compact_kernel<8>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, *compact);
+    return hipGetLastError();
+}
+
+// ---- Tor v3 onion addresses (VGF_ONION): Ed25519 keys that WALK ------------------------------------------------------------------
+// Tor loads the scalar itself, so a, a + 8, a + 16, ... are all keys and A(a + 8 i) = A(a) + i (8B): the staging of the secp256k1
+// scan above carries over.  Every key is U_j + R_u or U_j - R_u (device_types.h: OnionArgs) for S = 32 points U_j the dispatch
+// shares (onion_points_kernel makes them at the head of the dispatch, from the fixed-base table) and one affine table point R_u per
+// lane; core/ed_walk.h has the formulas.  The pair's two denominators 1 -+ k need ONE product (k = e1 t2), so the forward kernel
+// computes nothing else:
+//   onion_fwd_kernel   per lane the 2 S denominators, their prefix products into device scratch (word-major: coalesced), then the
+//                      workgroup's lanes multiply their totals in the shuffle butterfly of ed_keys_kernel, the first wave inverts the
+//                      workgroup's product (ONE fe25_inv per 512 lanes = 32 768 keys), and every lane leaves 1 / (its total)
+//   onion_bwd_kernel   walks the lane's chain down (recomputing the denominators: a product is cheaper than parking them), and per pair
+//                      x1 x2, y1 y2 and the two y: 12 products a pair in all.  FILTER form: y alone is encoded and filter_eval_onion
+//                      runs on the eight words in registers (the sign bit is masked out there); a hit lane computes x (4 more products
+//                      for its pair) and writes the full 32 bytes; a lane's 32 + 32 verdicts are two aligned 32-bit words of the hit
+//                      mask, stored plainly; ptab_compact_kernel<8> makes the records.  DUMP form: x for every pair, every payload to
+//                      its slot, zero for the slot whose scalar is 0.  No atomics, no scratch memory of the private kind, no LDS
+//                      beyond the 576 B of the tree.
+// Neither addition has exceptional cases (d is a non-square), so no pair needs a flag and no denominator is 0.
+
+__global__ void __launch_bounds__(64) onion_points_kernel(const OnionPointsArgs a) {
+    const u32 i = blockIdx.x * 64u + threadIdx.x;
+    const bool live = i < a.n;
+    u32 s[8], k[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) s[q] = a.start[q];
+    (void)edw_add_u64(k, s, (u64)(live ? i : 0u) * a.step);
+    ed_pt p;
+    ed_mul_base(p, a.table, k);
+    fe25 zi, x, y, t;
+    fe25_inv(zi, p.Z);   // (a wave inverts 64 values in the time of one: no sharing needed for 32 points a dispatch)
+    fe25_mul(x, p.X, zi);
+    fe25_mul(y, p.Y, zi);
+    fe25_mul(t, x, y);
+    if (a.mul_d) {
+        fe25 d;
+        edw_d(d);
+        fe25_mul(t, t, d);
+    }
+    fe25_reduce(x);
+    fe25_reduce(y);
+    fe25_reduce(t);
+    if (!live) return;
+    u32 *o = a.out + (size_t)i * a.istride;
+#pragma unroll
+    for (int w = 0; w < 9; w++) {
+        o[(size_t)w * a.wstride] = x.n[w];
+        o[(size_t)(9 + w) * a.wstride] = y.n[w];
+        o[(size_t)(18 + w) * a.wstride] = t.n[w];
+    }
+}
+
+__device__ __forceinline__ void onion_load_fe(fe25 &r, const u32 *p, size_t stride) {
+#pragma unroll
+    for (int w = 0; w < 9; w++) r.n[w] = p[(size_t)w * stride];
+}
+
+__global__ void __launch_bounds__(ONION_WG) onion_fwd_kernel(const OnionArgs a) {
+    constexpr int WAVES = ONION_WG / 64;
+    static_assert(WAVES == 8, "the second butterfly below has log2(WAVES) = 3 levels");
+    __shared__ u32 wave_total[WAVES][9], wave_inv[WAVES][9];
+    const u32 g = blockIdx.x * (u32)ONION_WG + threadIdx.x;
+    const u32 wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const size_t L = a.lanes;
+    const bool live = g < a.lanes;
+    const u32 gl = live ? g : 0u;   // (lanes past the table read lane 0's point and store nothing: every lane takes part in the tree)
+    fe25 t2, acc;
+    onion_load_fe(t2, a.lane + 18 * L + gl, L);
+    fe25_set_one(acc);
+#pragma unroll 1
+    for (int j = 0; j < ONION_S; j++) {
+        fe25 e1, dm, dp;
+        onion_load_fe(e1, a.uni + j * ONION_PT_WORDS + 18, 1);
+        edw_dens(dm, dp, e1, t2);
+        u32 *o = a.pre + (size_t)(2 * j) * 9 * L + gl;
+        if (live) {
+#pragma unroll
+            for (int w = 0; w < 9; w++) o[(size_t)w * L] = acc.n[w];
+        }
+        fe25_mul(acc, acc, dm);
+        if (live) {
+#pragma unroll
+            for (int w = 0; w < 9; w++) o[(size_t)(9 + w) * L] = acc.n[w];
+        }
+        fe25_mul(acc, acc, dp);
+    }
+    if (!live) fe25_set_one(acc);
+    fe25 total = acc, co;
+    ed_butterfly<6>(total, co);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; q++) wave_total[wave][q] = total.n[q];
+    }
+    __syncthreads();
+    if (wave == 0) {
+        fe25 t, c, inv;
+        fe25_set_one(t);
+        if (lane < (u32)WAVES) {
+#pragma unroll
+            for (int q = 0; q < 9; q++) t.n[q] = wave_total[lane][q];
+        }
+        ed_butterfly<3>(t, c);
+        fe25_inv(inv, t);
+        fe25_mul(inv, inv, c);   // 1 / (the total of wave `lane`)
+        if (lane < (u32)WAVES) {
+#pragma unroll
+            for (int q = 0; q < 9; q++) wave_inv[lane][q] = inv.n[q];
+        }
+    }
+    __syncthreads();
+    fe25 zi;
+#pragma unroll
+    for (int q = 0; q < 9; q++) zi.n[q] = wave_inv[wave][q];
+    fe25_mul(zi, zi, co);        // 1 / (this lane's total)
+    if (live) {
+#pragma unroll
+        for (int w = 0; w < 9; w++) a.inv[(size_t)w * L + g] = zi.n[w];
+    }
+}
+
+__device__ __forceinline__ void onion_store_payload(u32 *payloads, u32 slot, const u32 pl[8]) {
+    uint4 *o = reinterpret_cast<uint4 *>(payloads + (size_t)slot * 8);
+    o[0] = make_uint4(pl[0], pl[1], pl[2], pl[3]);
+    o[1] = make_uint4(pl[4], pl[5], pl[6], pl[7]);
+}
+
+template <bool DUMP>
+__global__ void __launch_bounds__(ONION_WG) onion_bwd_kernel(const OnionArgs a) {
+    const u32 g = blockIdx.x * (u32)ONION_WG + threadIdx.x;
+    if (g >= a.lanes) return;   // (no cross-lane step below)
+    const size_t L = a.lanes;
+    edw_pt q;
+    onion_load_fe(q.x, a.lane + g, L);
+    onion_load_fe(q.y, a.lane + 9 * L + g, L);
+    onion_load_fe(q.t, a.lane + 18 * L + g, L);
+    fe25 run;
+    onion_load_fe(run, a.inv + g, L);
+    const u32 slot_p = (a.lanes + g) * (u32)ONION_S, slot_m = (a.lanes - 1u - g) * (u32)ONION_S;
+    u32 hit_p = 0, hit_m = 0;
+#pragma unroll 1
+    for (int j = ONION_S - 1; j >= 0; j--) {
+        edw_pt p;
+        const u32 *u = a.uni + j * ONION_PT_WORDS;
+        onion_load_fe(p.x, u, 1);
+        onion_load_fe(p.y, u + 9, 1);
+        onion_load_fe(p.t, u + 18, 1);
+        fe25 dm, dp, pr, im, ip;
+        edw_dens(dm, dp, p.t, q.t);
+        const u32 *e = a.pre + (size_t)(2 * j) * 9 * L + g;
+        onion_load_fe(pr, e + 9 * L, L);
+        fe25_mul(ip, run, pr);
+        fe25_mul(run, run, dp);
+        onion_load_fe(pr, e, L);
+        fe25_mul(im, run, pr);
+        fe25_mul(run, run, dm);
+        fe25 ys, yd;
+        edw_pair_y(ys, yd, p, q, im, ip);
+        u32 ps[8], pd[8];
+        edw_encode_y(ps, ys);
+        edw_encode_y(pd, yd);
+        const u32 sp = slot_p + (u32)j, sm = slot_m + (u32)j;
+        bool want_p = true, want_m = true;
+        if (!DUMP) {
+            want_p = sp != a.zero_slot && filter_eval_onion(a.filter, ps);
+            want_m = sm != a.zero_slot && filter_eval_onion(a.filter, pd);
+            hit_p |= (want_p ? 1u : 0u) << j;
+            hit_m |= (want_m ? 1u : 0u) << j;
+        }
+        if (want_p || want_m) {
+            fe25 xs, xd;
+            edw_pair_x(xs, xd, p, q, im, ip);
+            ps[7] |= edw_sign(xs) << 31;
+            pd[7] |= edw_sign(xd) << 31;
+            if (DUMP) {
+#pragma unroll
+                for (int w = 0; w < 8; w++) {
+                    ps[w] = sp == a.zero_slot ? 0u : ps[w];
+                    pd[w] = sm == a.zero_slot ? 0u : pd[w];
+                }
+            }
+            if (want_p) onion_store_payload(a.payloads, sp, ps);
+            if (want_m) onion_store_payload(a.payloads, sm, pd);
+        }
+    }
+    if (!DUMP) {
+        a.hits[a.lanes + g] = hit_p;
+        a.hits[a.lanes - 1u - g] = hit_m;
+    }
+}
+
+hipError_t launch_onion_points(const OnionPointsArgs &a, hipStream_t stream) {
+    if (!a.table || !a.out || a.n == 0 || a.wstride == 0 || a.istride == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(onion_points_kernel, dim3((a.n + 63) / 64), dim3(64), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_onion(const OnionArgs &a, uint32_t batch, const PtabArgs *compact, hipStream_t stream, hipEvent_t before_bwd) {
+    if (batch == 0 || a.lanes == 0 || (uint64_t)a.lanes * 2 * ONION_S != batch || !a.uni || !a.lane || !a.pre || !a.inv || !a.payloads)
+        return hipErrorInvalidValue;
+    if (compact && (!a.hits || !a.filter || compact->payloads != a.payloads || (const void *)compact->hits != (const void *)a.hits ||
+                    compact->stride != batch || compact->count != batch || compact->images != 1 || !compact->mhdr || !compact->mrec))
+        return hipErrorInvalidValue;
+    const dim3 grid((a.lanes + ONION_WG - 1) / ONION_WG);
+    hipLaunchKernelGGL(onion_fwd_kernel, grid, dim3(ONION_WG), 0, stream, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (before_bwd && (e = hipEventRecord(before_bwd, stream)) != hipSuccess) return e;
+    if (!compact) {
+        hipLaunchKernelGGL((onion_bwd_kernel<true>), grid, dim3(ONION_WG), 0, stream, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((onion_bwd_kernel<false>), grid, dim3(ONION_WG), 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL((ptab_compact_kernel<8>), dim3(1), dim3(PTAB_COMPACT_WG), 0, stream, *compact);
     return hipGetLastError();
 }

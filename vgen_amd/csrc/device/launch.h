@@ -70,4 +70,11 @@ hipError_t launch_create3_score(const Create3ScoreArgs &a, bool guarded, uint32_
 // A Solana dispatch (VGF_SOLANA): one seed per thread, `batch` (a multiple of ED_WG) lanes of which the first a.n have a key; SHA-512,
 // the Ed25519 fixed-base multiplication, one inversion per workgroup.  `compact` as for launch_create2, over eight-word slots.
 hipError_t launch_ed_keys(const EdArgs &a, uint32_t batch, const PtabArgs *compact, hipStream_t stream);
+// The onion walk (VGF_ONION).  launch_onion_points: a.n points (start + i step) B as affine limbs - the context's lane table once, the
+// S shared points of every dispatch.  launch_onion: `batch` = 2 ONION_S a.lanes keys as U_j +- R_u - onion_fwd_kernel (prefix products
+// of the denominators into a.pre, one inversion per workgroup, the lanes' inverses into a.inv), `before_bwd` (optional) recorded, then
+// onion_bwd_kernel: compact == nullptr writes every payload to a.payloads, otherwise the filter form writes a.hits and the payloads of
+// hit slots and the list path's compaction follows, as for launch_create2, over eight-word slots.
+hipError_t launch_onion_points(const OnionPointsArgs &a, hipStream_t stream);
+hipError_t launch_onion(const OnionArgs &a, uint32_t batch, const PtabArgs *compact, hipStream_t stream, hipEvent_t before_bwd);
 }  // namespace vg

@@ -2,6 +2,7 @@
 #include "encode.h"
 
 #include "ed_host.h"
+#include "onion_host.h"
 
 #include <ctype.h>
 #include <string.h>
@@ -371,6 +372,13 @@ std::string address_from_payload(uint32_t format, const uint8_t *payload) {
         return nip19_encode("npub", payload);
     case VGF_SOLANA:   // the 32 bytes as one big-endian number, no version, no checksum; a leading zero byte is a leading '1'
         return base58_encode(payload, 32);
+    case VGF_ONION: {  // Base32 of the key, its SHA3-256 checksum and the version byte (without ".onion")
+        // An all-zero payload is the dump's "no key" mark (the slot whose scalar is 0), and as a key it is y = 0, a point of order 4,
+        // which Tor refuses as an onion service's identity: it has no address (vgen_onion_encode encodes any 32 bytes).
+        uint8_t any = 0;
+        for (int i = 0; i < 32; i++) any |= payload[i];
+        return any ? onion_encode(payload) : std::string();
+    }
     default:
         return std::string();
     }
@@ -380,6 +388,7 @@ std::string key_to_wif(uint32_t format, const uint8_t key_be[32]) {
     if (vgf_is_eth((int)format)) return hex_lower(key_be, 32);
     if (format == VGF_NOSTR) return nip19_encode("nsec", key_be);
     if (format == VGF_SOLANA) return hex_lower(key_be, 32);   // the seed (the 88-character keypair string: solana_keypair_base58)
+    if (format == VGF_ONION) return hex_lower(key_be, 32);    // the scalar's 32 LITTLE-endian bytes (the expanded key: onion_expand)
     uint8_t buf[34];
     buf[0] = 0x80;
     memcpy(buf + 1, key_be, 32);
@@ -402,6 +411,10 @@ static void fe_to_be32(const fe &a, uint8_t out[32]) {
 int payload_from_key(uint32_t format, const uint8_t key_be[32], uint8_t out[32]) {
     if (format == VGF_SOLANA) {   // the key is an Ed25519 seed, any 32 bytes
         ed_public_key(key_be, out);
+        return 32;
+    }
+    if (format == VGF_ONION) {    // the key is the Ed25519 scalar itself, 32 little-endian bytes
+        onion_public_key(key_be, out);
         return 32;
     }
     Scalar k;

@@ -6,6 +6,7 @@
 #include "../core/ptab_eval.h"
 #include "../core/score_eval.h"
 #include "ed_host.h"
+#include "onion_host.h"
 #include "encode.h"
 
 #include <string.h>
@@ -694,6 +695,61 @@ void derive_symbols(const Dfa &d, const SymSpec &sp, DevFilter &dev, double &sel
     // count == 0 means nothing can match: the kernel then reports no candidates
 }
 
+// ---- Tor v3 onion addresses: 56 Base32 characters of key || checksum || version --------------------------------------------------
+// Characters 0 .. 48 are bits 0 .. 244 of the key's byte stream - y alone; the sign of x is stream bit 248, the checksum a SHA3-256
+// the device does not compute.  So the device test is the masked compare of a START-ANCHORED prefix (classes and -i included: up to
+// DEVF_MAX_TESTS accepted prefixes, the shallowest enumeration of the best selectivity, no deeper than 49 characters) and nothing
+// else: suffixes, unanchored patterns and whatever constrains later characters only are DEVF_HOST_ALL.  Always a superset.
+const char B32[] = "abcdefghijklmnopqrstuvwxyz234567";
+
+void derive_onion(const Dfa &d, DevFilter &dev, double &sel) {
+    dev.kind = DEVF_HOST_ALL;
+    dev.count = 0;
+    dev.flags = 0;
+    sel = 1.0;
+    if (d.match_now[0]) {
+        dev.kind = DEVF_ALL;
+        return;
+    }
+    const SymSpec sp = {"", B32, 5, 49, 0, 256, 49};
+    std::vector<Prefix> prefixes;
+    double prefix_sel = 1.0;
+    bool have = false;
+    for (size_t depth = 1; depth <= 49; depth++) {
+        std::vector<Prefix> p;
+        if (!enumerate_prefixes(d, 0, B32, depth, 100000, p) || p.size() > DEVF_MAX_TESTS) break;
+        double sel_d = 0;
+        bool exact = true;
+        for (auto &q : p) {
+            double f = 1.0;
+            for (size_t i = 0; i < q.s.size(); i++) f /= 32.0;
+            sel_d += f;
+            exact = exact && q.absorbing;
+        }
+        if (!have || sel_d < prefix_sel * (1.0 - 1e-9)) {
+            prefixes.swap(p);
+            prefix_sel = sel_d;
+            have = true;
+        }
+        if (exact) {        // nothing deeper to learn
+            if (sel_d > 0.999999) {   // every string of this depth is accepted whatever follows: every address matches
+                dev.kind = DEVF_ALL;
+                return;
+            }
+            break;
+        }
+    }
+    if (!have || prefix_sel > 0.2) return;   // not a useful necessary condition: the host filters
+    dev.kind = DEVF_MASKED;
+    sel = prefix_sel;
+    for (auto &p : prefixes) {
+        DevFilterTest t;
+        memset(&t, 0, sizeof t);
+        for (size_t i = 0; i < p.s.size(); i++) (void)set_symbol(sp, t, (unsigned)i, (unsigned)sym_index(sp, p.s[i]));
+        dev.tests[dev.count++] = t;
+    }
+}
+
 // Packs `d` into the device layout of core/dfa_eval.h.  `head` is the literal every address of the format
 // starts with and that the device does not re-walk; `alphabet` maps symbol index -> character.
 // Returns false when the automaton does not fit the LDS budget (or 16-bit state numbers).
@@ -952,6 +1008,9 @@ bool filter_compile(const std::string &pattern, bool case_insensitive, uint32_t 
     }
     case VGF_SOLANA:
         derive_solana(out.dfa, out.dev, out.selectivity);
+        break;
+    case VGF_ONION:
+        derive_onion(out.dfa, out.dev, out.selectivity);
         break;
     case VGF_P2TR: {
         // bc1p + 52 data symbols (256 bits + 4 pad bits) + 6 Bech32m checksum symbols
@@ -1274,6 +1333,8 @@ bool payload_from_address(uint32_t format, const std::string &address, uint8_t o
         return nip19_decode("npub", a, out);   // (strict: header, length, case, pad bits, checksum)
     } else if (format == VGF_SOLANA) {
         return solana_decode(a, out);          // (strict: the alphabet, exactly 32 bytes)
+    } else if (format == VGF_ONION) {
+        return onion_decode(a, out);           // (strict: length, lower case, the alphabet, version, checksum)
     } else if (format == VGF_P2WPKH || format == VGF_P2TR) {
         const size_t n_data = format == VGF_P2TR ? 52 : 32, len = 4 + n_data + 6;
         if (a.size() != len) return false;

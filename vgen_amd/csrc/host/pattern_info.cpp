@@ -11,7 +11,7 @@
 namespace vg {
 namespace {
 
-enum class Charset { Base58, Bech32, Hex, None };
+enum class Charset { Base58, Bech32, Hex, Base32, None };
 
 Charset charset_of(unsigned format) {
     switch ((int)format) {
@@ -25,6 +25,7 @@ Charset charset_of(unsigned format) {
     case VGF_ETHEREUM:
     case VGF_ETHEREUM_CONTRACT:
     case VGF_ETHEREUM_CREATE2: return Charset::Hex;
+    case VGF_ONION: return Charset::Base32;   // (RFC 4648, lower case; no constant prefix)
     default: return Charset::None;
     }
 }
@@ -35,6 +36,7 @@ const char *alphabet_of(Charset cs) {
     case Charset::Base58: return "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz";
     case Charset::Bech32: return "023456789acdefghjklmnpqrstuvwxyz";
     case Charset::Hex: return "0123456789abcdefABCDEFx";
+    case Charset::Base32: return "abcdefghijklmnopqrstuvwxyz234567";
     default: return "";
     }
 }
@@ -132,6 +134,7 @@ const char *format_charset_name(unsigned format) {
     case Charset::Base58: return "Base58";
     case Charset::Bech32: return "Bech32";
     case Charset::Hex: return "Hex";
+    case Charset::Base32: return "Base32";
     default: return nullptr;
     }
 }
@@ -186,7 +189,7 @@ uint64_t pattern_difficulty(const std::string &p, bool case_insensitive, unsigne
         return d;
     }
     const Charset cs = charset_of(format);
-    const uint64_t alphabet = cs == Charset::Base58 ? (case_insensitive ? 34 : 58) : cs == Charset::Bech32 ? 32 : 16;
+    const uint64_t alphabet = cs == Charset::Base58 ? (case_insensitive ? 34 : 58) : (cs == Charset::Bech32 || cs == Charset::Base32) ? 32 : 16;
     unsigned fixed = pattern_fixed_chars(p);
 
     // characters of the format's constant prefix that an anchored pattern spells out (pattern.rs:205-244)

@@ -10,6 +10,7 @@
 
 #include "../../../include/vgen_hip.h"
 #include "ed_host.h"
+#include "onion_host.h"
 #include "encode.h"
 #include "filter.h"
 #include "scalar.h"
@@ -113,6 +114,21 @@ inline bool make_match(const vgen_filter &flt, uint32_t format, const BatchKeys 
         for (int i = 0; i < 8; i++)
             for (int b = 0; b < 4; b++) g.key[4 * i + b] = (uint8_t)(d[7 - i] >> (8 * (3 - b)));
         ed_public_key(g.key, mine);
+        if (memcmp(mine, payload, 32) != 0) {
+            if (bk.dropped) bk.dropped->fetch_add(1, std::memory_order_relaxed);
+            return false;
+        }
+        memcpy(g.address, addr.c_str(), addr.size() + 1);
+        return true;
+    }
+    if (format == VGF_ONION) {
+        // The key is the scalar base(seed, stream) + 8 (first_index + index), little-endian.  Its public key is re-derived here (scalar x B
+        // with the host build of the device's headers) and a candidate whose payload differs is dropped: one multiplication per MATCH.
+        if (!bk.random) return false;   // (the scan loop names every batch by its stream and first index)
+        uint8_t base[32], mine[32];
+        onion_base(bk.seed, bk.stream, base);
+        if (!onion_scalar_at(base, bk.first_index + index, g.key)) return false;
+        onion_public_key(g.key, mine);
         if (memcmp(mine, payload, 32) != 0) {
             if (bk.dropped) bk.dropped->fetch_add(1, std::memory_order_relaxed);
             return false;

@@ -14,6 +14,7 @@
 #include "core/hash.h"
 #include "device/launch.h"
 #include "core/ed25519.h"
+#include "core/ed_walk.h"
 #include "host/ed_host.h"
 #include "host/host_ec.h"
 
@@ -75,6 +76,7 @@ size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
 void release_gtab(vgen_ctx *c);   // (defined with the generator-table cache below)
 void release_edtab(vgen_ctx *c);  // (the Ed25519 table's cache, beside the Solana dispatches)
 int acquire_edtab(vgen_ctx *c);
+int onion_create(vgen_ctx *c);   // (the onion walk's tables and scratch, beside its dispatch)
 bool mem_allows(vgen_ctx *c, uint64_t extra, bool table, bool by_name, std::string *why);   // (the memory policy, same place)
 
 // Frame i's stream, created on first use (a stream costs ~5-8 ms: a scan's first dispatches should be running while
@@ -274,7 +276,7 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
         err = "device index out of range";
         return VGEN_E_NODEVICE;
     }
-    if (p->format > VGF_ETHEREUM_CREATE2 && p->format != VGF_NOSTR && p->format != VGF_SOLANA) {
+    if (p->format > VGF_ETHEREUM_CREATE2 && p->format != VGF_NOSTR && p->format != VGF_SOLANA && p->format != VGF_ONION) {
         err = "unknown address format";
         return VGEN_E_INVALID;
     }
@@ -284,6 +286,10 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
     }
     if (p->format == VGF_SOLANA && (p->flags & VGEN_FLAG_ENDO)) {
         err = "VGEN_FLAG_ENDO: the endomorphism images belong to secp256k1; a solana search has none";
+        return VGEN_E_UNSUPPORTED;
+    }
+    if (p->format == VGF_ONION && (p->flags & VGEN_FLAG_ENDO)) {
+        err = "VGEN_FLAG_ENDO: the endomorphism images belong to secp256k1; an onion search has none";
         return VGEN_E_UNSUPPORTED;
     }
     const bool trace = getenv("VGEN_TRACE_CREATE") != nullptr;
@@ -386,6 +392,22 @@ int rt_create(const vgen_params *p_in, vgen_ctx **out, std::string &err) {
         lap("filter + match rings");
         if (int rc = acquire_edtab(c)) return bail(rc, c->err);
         lap("ed25519 table");
+        *out = c;
+        return VGEN_OK;
+    }
+    if (c->format == VGF_ONION) {
+        // the other curve, walked: none of the secp256k1 scratch or tables - the filter program, the match rings, the device's Ed25519
+        // table, this context's lane points and the frames' walk scratch here; dump and list buffers at their first use
+        if (c->batch % (2u * ONION_S) != 0) return bail(VGEN_E_INVALID, "batch_size must be a multiple of 64");
+        e = hipMalloc((void **)&c->d_filter, sizeof(DevFilter));
+        if (e != hipSuccess) return bail(VGEN_E_NOMEM, std::string("hipMalloc(filter): ") + hipGetErrorString(e));
+        c->frames_bytes += sizeof(DevFilter);
+        if (int rc = rt_set_match_cap(c, c->match_cap)) return bail(rc, c->err);
+        lap("filter + match rings");
+        if (int rc = acquire_edtab(c)) return bail(rc, c->err);
+        lap("ed25519 table");
+        if (int rc = onion_create(c)) return bail(rc, c->err);
+        lap("onion lane points + scratch");
         *out = c;
         return VGEN_OK;
     }
@@ -549,6 +571,8 @@ void rt_destroy(vgen_ctx *c) {
     release_gtab(c);                              // the wide table is shared per device: freed with its last user
     release_edtab(c);                             // ... and so is the Ed25519 table
     if (c->d_seed_slab) (void)hipFree(c->d_seed_slab);
+    if (c->d_onion_lane) (void)hipFree(c->d_onion_lane);
+    if (c->d_onion_slab) (void)hipFree(c->d_onion_slab);
     if (c->d_chk_lut) (void)hipFree(c->d_chk_lut);
     if (c->d_dfa) (void)hipFree(c->d_dfa);
     if (c->d_filter) (void)hipFree(c->d_filter);
@@ -652,7 +676,7 @@ bool deferred_filter(const vgen_ctx *c) {
 // then the compaction alone.
 // The Nostr per-key kernels do the same (xonly_bwd_kernel<PRE>, keys_xonly_kernel<PRE>): prefilter in registers, an atomic-free hit mask.
 bool inline_filter(const vgen_ctx *c) {
-    return (c->format == VGF_ETHEREUM_CREATE2 || c->format == VGF_NOSTR || c->format == VGF_SOLANA) && c->have_filter && !dump_mode(c) && !list_mode(c) &&
+    return (c->format == VGF_ETHEREUM_CREATE2 || c->format == VGF_NOSTR || vgf_is_ed((int)c->format)) && c->have_filter && !dump_mode(c) && !list_mode(c) &&
            !deferred_filter(c) && !score_mode(c);
 }
 
@@ -1475,6 +1499,126 @@ int enqueue_ed(vgen_ctx *c, uint32_t frame, const uint8_t *seeds_dev, const RndS
     return finish_dispatch(c, f, dump, n, false);
 }
 
+// ---- Tor v3 onion addresses (VGF_ONION) ---------------------------------------------------------------------------------------
+// Scratch of one frame: the dispatch's shared points | the prefix products (36 B per key) | the lanes' inverses.
+size_t onion_uni_bytes() { return up256((size_t)ONION_PT_WORDS * ONION_S * sizeof(uint32_t)); }
+size_t onion_pre_bytes(const vgen_ctx *c) { return up256((size_t)c->batch * 9 * sizeof(uint32_t)); }
+size_t onion_inv_bytes(const vgen_ctx *c) { return up256((size_t)c->onion_lanes * 9 * sizeof(uint32_t)); }
+size_t onion_frame_bytes(const vgen_ctx *c) { return onion_uni_bytes() + onion_pre_bytes(c) + onion_inv_bytes(c); }
+size_t onion_lane_bytes(const vgen_ctx *c) { return up256((size_t)c->onion_lanes * ONION_PT_WORDS * sizeof(uint32_t)); }
+
+int enqueue_onion(vgen_ctx *c, uint32_t frame, const uint8_t base_le[32], uint64_t first);
+
+// The lane points R_u = (u S + S/2) (8B), u < batch / (2 S): built once, on the device, from the Ed25519 table; and the frames' scratch.
+int onion_create(vgen_ctx *c) {
+    c->onion_lanes = c->batch / (2u * ONION_S);
+    const uint64_t need = (uint64_t)onion_lane_bytes(c) + (uint64_t)onion_frame_bytes(c) * c->frames;
+    const uint64_t fixed = sizeof(DevFilter) + (uint64_t)up256(match_bytes(c->match_cap)) * c->frames + ED_TABLE_WORDS * sizeof(uint32_t);
+    if (c->mem_budget && fixed + need > c->mem_budget)
+        return c->fail(VGEN_E_NOMEM, "device_mem_budget_bytes " + std::to_string(c->mem_budget) + " does not cover the frames and the tables: " +
+                                         std::to_string(fixed + need) + " bytes");
+    if (hipMalloc((void **)&c->d_onion_lane, onion_lane_bytes(c)) != hipSuccess) return c->fail(VGEN_E_NOMEM, "onion lane-point table allocation failed");
+    if (hipMalloc((void **)&c->d_onion_slab, onion_frame_bytes(c) * c->frames) != hipSuccess) return c->fail(VGEN_E_NOMEM, "onion walk scratch allocation failed");
+    c->frames_bytes += (uint64_t)onion_frame_bytes(c) * c->frames;
+    for (uint32_t i = 0; i < c->frames; i++) c->fr[i].d_scratch = reinterpret_cast<uint32_t *>(c->d_onion_slab + onion_frame_bytes(c) * i);
+    OnionPointsArgs a;
+    memset(&a, 0, sizeof a);
+    a.table = c->d_edtab;
+    a.start[0] = 8u * (ONION_S / 2);
+    a.step = 8u * ONION_S;
+    a.n = c->onion_lanes;
+    a.mul_d = 0;
+    a.wstride = c->onion_lanes;
+    a.istride = 1;
+    a.out = c->d_onion_lane;
+    // (on frame 0's stream and waited for, like every other setup of a context: the null stream would take a hardware queue of its
+    //  own away from the frames' twelve)
+    hipStream_t st0 = nullptr;
+    if (int rc = frame_stream(c, 0, &st0)) return rc;
+    HIP_TRY(c, launch_onion_points(a, st0));
+    HIP_TRY(c, hipStreamSynchronize(st0));
+    c->onion_dispatch = enqueue_onion;
+    return VGEN_OK;
+}
+
+// vgen_dispatch_onion: candidate i has the scalar base + 8 (first + i).  Everything is checked before anything is enqueued.
+int enqueue_onion(vgen_ctx *c, uint32_t frame, const uint8_t base_le[32], uint64_t first) {
+    if (frame >= c->frames || !base_le) return c->fail(VGEN_E_INVALID, "bad frame index / base scalar");
+    vgen_ctx::Frame &f = c->fr[frame];
+    if (f.in_flight) return c->fail(VGEN_E_STATE, "frame already has a dispatch in flight");
+    if (base_le[0] & 7) return c->fail(VGEN_E_INVALID, "vgen_dispatch_onion: the base scalar must be a multiple of 8 (Tor multiplies by the cofactor)");
+    u32 base[8], lo[8], hi[8], uni[8];
+    for (int i = 0; i < 8; i++) base[i] = (u32)base_le[4 * i] | (u32)base_le[4 * i + 1] << 8 | (u32)base_le[4 * i + 2] << 16 | (u32)base_le[4 * i + 3] << 24;
+    // base + 8 first and base + 8 (first + batch - 1): 8 first is below 2^67, added as two 64-bit pieces
+    const uint64_t last = (uint64_t)c->batch - 1, mid = (uint64_t)c->onion_lanes * ONION_S - ONION_S / 2;
+    u32 carry = edw_add_u64(lo, base, first << 3);
+    u32 top[8] = {0, 0, (u32)(first >> 61), 0, 0, 0, 0, 0};
+    {
+        uint64_t cy = 0;
+        for (int i = 0; i < 8; i++) {
+            cy += (uint64_t)lo[i] + top[i];
+            lo[i] = (u32)cy;
+            cy >>= 32;
+        }
+        carry |= (u32)cy;
+    }
+    carry |= edw_add_u64(hi, lo, last << 3);
+    if (carry || (hi[7] >> 31) || (base[7] >> 31))
+        return c->fail(VGEN_E_RANGE, "vgen_dispatch_onion: base + 8 (first_index + batch_size - 1) reaches 2^255");
+    (void)edw_add_u64(uni, lo, mid << 3);   // (below hi)
+    bool zero = true;
+    for (int i = 0; i < 8; i++) zero = zero && lo[i] == 0;
+    if (c->injected_fault()) return c->fail(VGEN_E_HIP, "injected device failure (vgen_debug_fail_after)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = ensure_frame(c, frame)) return rc;
+    const bool dump = dump_mode(c);
+    uint8_t *slab = reinterpret_cast<uint8_t *>(f.d_scratch);
+    OnionPointsArgs pa;
+    memset(&pa, 0, sizeof pa);
+    pa.table = c->d_edtab;
+    memcpy(pa.start, uni, sizeof pa.start);
+    pa.step = 8;
+    pa.n = ONION_S;
+    pa.mul_d = 1;
+    pa.wstride = 1;
+    pa.istride = ONION_PT_WORDS;
+    pa.out = reinterpret_cast<uint32_t *>(slab);
+    OnionArgs a;
+    memset(&a, 0, sizeof a);
+    a.uni = pa.out;
+    a.lane = c->d_onion_lane;
+    a.pre = reinterpret_cast<uint32_t *>(slab + onion_uni_bytes());
+    a.inv = reinterpret_cast<uint32_t *>(slab + onion_uni_bytes() + onion_pre_bytes(c));
+    a.lanes = c->onion_lanes;
+    a.zero_slot = zero ? 0u : ONION_NO_SLOT;
+    PtabArgs p;
+    memset(&p, 0, sizeof p);
+    if (dump) {
+        if (int rc = ensure_dump_frame(c, frame)) return rc;
+        a.payloads = f.d_dump;
+    } else {
+        if (!inline_filter(c)) return c->fail(VGEN_E_UNSUPPORTED, "an onion context takes single patterns only (no lists, no scores)");
+        if (!f.d_list) return c->fail(VGEN_E_STATE, "the context's filter has no list buffers");   // (made by vgen_set_filter)
+        a.payloads = f.d_list;
+        a.hits = reinterpret_cast<uint32_t *>(f.d_hits);
+        a.filter = c->d_filter;
+        p.payloads = f.d_list;
+        p.hits = f.d_hits;
+        p.mhdr = reinterpret_cast<DevMatchHeader *>(f.d_match);
+        p.mrec = reinterpret_cast<DevMatch *>(f.d_match + sizeof(DevMatchHeader));
+        p.stride = c->batch;
+        p.count = c->batch;
+        p.images = 1;
+        p.match_base = f.match_base;
+        p.match_cap = c->match_cap;
+    }
+    memset(&f.start, 0, sizeof f.start);
+    if (c->timing) HIP_TRY(c, hipEventRecord(f.ev_start, f.s));
+    HIP_TRY(c, launch_onion_points(pa, f.s));
+    HIP_TRY(c, launch_onion(a, c->batch, dump ? nullptr : &p, f.s, c->timing ? f.ev_mid : nullptr));
+    return finish_dispatch(c, f, dump, c->batch, false);
+}
+
 }  // namespace
 
 // A CREATE2 context walks salts, not keys: the key dispatches refuse it.
@@ -1486,6 +1630,8 @@ int rt_dispatch(vgen_ctx *c, uint32_t frame, const uint8_t start_key_be[32]) {
     if (c->format == VGF_ETHEREUM_CREATE2) return refuse_create2(c, "vgen_dispatch");
     if (c->format == VGF_SOLANA)
         return c->fail(VGEN_E_UNSUPPORTED, "vgen_dispatch: a solana key is a seed and its scalar a hash of it - there is no walk; use vgen_dispatch_random / vgen_dispatch_keys");
+    if (c->format == VGF_ONION)
+        return c->fail(VGEN_E_UNSUPPORTED, "vgen_dispatch: an onion context walks Ed25519 scalars in steps of 8 - use vgen_dispatch_onion");
     if (frame >= c->frames || !start_key_be) return c->fail(VGEN_E_INVALID, "bad frame index / key");
     vgen_ctx::Frame &f = c->fr[frame];
     if (f.in_flight) return c->fail(VGEN_E_STATE, "frame already has a dispatch in flight");
@@ -1890,6 +2036,7 @@ int rt_get_memory(const vgen_ctx *c, vgen_memory_info *out) {
     out->frames_bytes = c->frames_bytes;
     out->mode_bytes = c->mode_bytes;
     out->table_bytes = gtab_held_bytes(c) + (c->d_edtab ? ED_TABLE_WORDS * sizeof(uint32_t) : 0);   // (the Ed25519 table of a Solana context)
+    if (c->d_onion_lane) out->table_bytes += (uint64_t)c->onion_lanes * ONION_PT_WORDS * sizeof(uint32_t);   // (an onion context's lane points)
     out->pinned_host_bytes = c->pinned_bytes;
     out->budget_bytes = c->mem_budget;
     size_t free_b = 0, total_b = 0;

@@ -114,6 +114,13 @@ struct vgen_ctx {
     // contexts there: a reference, not owned) and the frames' seed buffers of vgen_dispatch_keys (Frame::d_keys; made at first use)
     uint32_t *d_edtab = nullptr;
     uint8_t *d_seed_slab = nullptr;
+    // VGF_ONION: the walk's lane points ([ONION_PT_WORDS][onion_lanes], built on the device at vgen_create from d_edtab) and the frames'
+    // walk scratch (Frame::d_scratch: the dispatch's shared points | prefix products | the lanes' inverses), both owned; and the device
+    // side of vgen_dispatch_onion, set by the runtime that created the context (nullptr on every other context), as create2_dispatch
+    uint32_t *d_onion_lane = nullptr;
+    uint8_t *d_onion_slab = nullptr;
+    uint32_t onion_lanes = 0;
+    int (*onion_dispatch)(vgen_ctx *, uint32_t frame, const uint8_t base_scalar_le[32], uint64_t first_index) = nullptr;
 
     struct Frame {
         hipStream_t s = nullptr;         // this frame's stream (owned by the context): carries the whole dispatch chain
@@ -247,6 +254,10 @@ inline int rt_set_create3(vgen_ctx *ctx, const uint8_t factory[20], const uint8_
 inline int rt_dispatch_create2(vgen_ctx *ctx, uint32_t frame, uint64_t first_counter) {
     if (!ctx->create2_dispatch) return ctx->fail(VGEN_E_INVALID, "vgen_dispatch_create2: the context was not created for the ethereum-create2 format (7)");
     return ctx->create2_dispatch(ctx, frame, first_counter);
+}
+inline int rt_dispatch_onion(vgen_ctx *ctx, uint32_t frame, const uint8_t base_scalar_le[32], uint64_t first_index) {
+    if (!ctx->onion_dispatch) return ctx->fail(VGEN_E_INVALID, "vgen_dispatch_onion: the context was not created for the onion format (13)");
+    return ctx->onion_dispatch(ctx, frame, base_scalar_le, first_index);
 }
 int rt_get_memory(const vgen_ctx *ctx, vgen_memory_info *out);
 int rt_get_resources(const vgen_ctx *ctx, uint32_t *dump_frames, uint32_t *table_bits, uint32_t *table_bits_wanted, std::string *note);

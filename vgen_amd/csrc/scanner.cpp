@@ -303,7 +303,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
     // This is a PREFERENCE: the caller bounds it (cfg->table_bits_max, vgen_params.table_bits / device_mem_budget_bytes), the runtime
     // checks it against the device's free memory, builds the wider table in the background while this loop dispatches on the one
     // it has, and takes it into use when it is complete (runtime.cpp) — the scan never waits for a table.
-    if ((random_keys || ctx->format == VGF_P2TR) && ctx->format != VGF_SOLANA) {   // (a Solana context has no generator table to widen)
+    if ((random_keys || ctx->format == VGF_P2TR) && !vgf_is_ed((int)ctx->format)) {   // (a Solana or onion context has no generator table to widen)
         // (a count-limited scan whose pattern has no selectivity estimate — the whole DFA on the device — is taken for short)
         double keys = cfg->count == UINT64_MAX ? 1e30 : 0.0;
         if (!host_all && flt.selectivity > 0 && cfg->count != UINT64_MAX) keys = (double)cfg->count / flt.selectivity;
@@ -394,7 +394,14 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
             }
             uint8_t sb[24];
             rnd_seed_to_bytes(rnd_seed, sb);
-            int r = vgen_dispatch_random_seed(ctx, frame, sb, shard, first);
+            int r;
+            if (ctx->format == VGF_ONION) {   // the walk: batch b of shard s is candidates b N .. of the base scalar of stream s
+                uint8_t base[32];
+                onion_base(rnd_seed, shard, base);
+                r = vgen_dispatch_onion(ctx, frame, base, first);   // (VGEN_E_RANGE, probability ~2^-187, ends the scan)
+            } else {
+                r = vgen_dispatch_random_seed(ctx, frame, sb, shard, first);
+            }
             if (r != VGEN_OK) return r;
             pend[frame] = BatchKeys{};
             pend[frame].batch_no = batch_no;
@@ -436,7 +443,7 @@ int scan_shard(vgen_ctx *ctx, const vgen_filter &flt, ScanJob &job, ResultSink &
     // A scan of the scalar-multiplication paths that turns out LONG although nothing said so up front (no selectivity estimate, a
     // count that keeps not being reached): after 5 s it asks for the 29-bit signed table (+12.5 % once it is there) and simply goes
     // on — the runtime builds it behind the dispatches (round 4 drained the frames and paused 0.7 - 2.3 s here).
-    const bool table_path = (random_keys || ctx->format == VGF_P2TR) && ctx->format != VGF_SOLANA;
+    const bool table_path = (random_keys || ctx->format == VGF_P2TR) && !vgf_is_ed((int)ctx->format);
     const auto scan_t0 = std::chrono::steady_clock::now();
     bool upgrade_asked = false;
     auto may_launch = [&]() { return can_dispatch() && !stopped() && !sink.done(); };
@@ -714,6 +721,24 @@ static int solana_scan_rules(vgen_ctx **ctxs, uint32_t n_ctx, vgen_scan_config &
     return VGEN_OK;
 }
 
+// Onion scans (VGF_ONION, context or configuration): every shard walks a + 8 i from the base scalar of its own stream of the seed, so
+// the scan runs the stream loop (the flag is implied: a batch is named by stream and first index, not by a secp256k1 start key); a
+// key range and checkpoints are not provided.  VGEN_OK, or the refusal.
+static int onion_scan_rules(vgen_ctx **ctxs, uint32_t n_ctx, vgen_scan_config &c, const char *what) {
+    bool any = c.format == VGF_ONION;
+    for (uint32_t i = 0; i < n_ctx; i++) any = any || ctxs[i]->format == VGF_ONION;
+    if (!any) return VGEN_OK;
+    vgen_ctx *c0 = ctxs[0];
+    for (uint32_t i = 0; i < n_ctx; i++)
+        if (ctxs[i]->format != VGF_ONION || c.format != VGF_ONION)
+            return c0->fail(VGEN_E_INVALID, std::string(what) + ": an onion scan needs the onion format (13) in the configuration and on every context");
+    if (c.has_start || c.has_end)
+        return c0->fail(VGEN_E_UNSUPPORTED, std::string(what) + ": an onion scan walks from the base scalar of its seed - there is no key range (has_start / has_end)");
+    if (c.checkpoint_path) return c0->fail(VGEN_E_UNSUPPORTED, std::string(what) + ": checkpoints are not provided for the onion format");
+    c.flags |= VGEN_SCAN_RANDOM_KEYS;
+    return VGEN_OK;
+}
+
 // ABI 4's vgen_scan_config, or ABI 3's 136 bytes (no table_bits_max: no cap): -> the full structure, fields beyond the caller's zero.
 static bool normalise_scan_config(const vgen_scan_config *in, vgen_scan_config &full) {
     constexpr uint32_t CONFIG_ABI3 = 136;
@@ -758,6 +783,7 @@ extern "C" int vgen_scan(vgen_ctx *ctx, const char *pattern, const vgen_scan_con
     memset(out, 0, sizeof *out);
     if (ctx->format == VGF_ETHEREUM_CREATE2 || c.format == VGF_ETHEREUM_CREATE2) return refuse_create2(ctx, "vgen_scan");
     if (int rc = solana_scan_rules(&ctx, 1, c, "vgen_scan")) return rc;
+    if (int rc = onion_scan_rules(&ctx, 1, c, "vgen_scan")) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     vgen_filter flt;
     std::string err;
@@ -1024,6 +1050,7 @@ extern "C" int vgen_scan_multi(vgen_ctx **ctxs, uint32_t n_ctx, const char *patt
     if (!pattern || !multi_args(ctxs, n_ctx, cfg_in, cfg_full, out)) return VGEN_E_INVALID;
     if (any_create2(ctxs, n_ctx, cfg_full)) return refuse_create2(ctxs[0], "vgen_scan_multi");
     if (int rc = solana_scan_rules(ctxs, n_ctx, cfg_full, "vgen_scan_multi")) return rc;
+    if (int rc = onion_scan_rules(ctxs, n_ctx, cfg_full, "vgen_scan_multi")) return rc;
     const vgen_scan_config *cfg = &cfg_full;
     vgen_filter flt;
     std::string err;
@@ -1043,6 +1070,8 @@ extern "C" int vgen_scan_list(vgen_ctx **ctxs, uint32_t n_ctx, const vgen_filter
     if (any_create2(ctxs, n_ctx, cfg_full)) return refuse_create2(ctxs[0], "vgen_scan_list");
     if (cfg_full.format == VGF_SOLANA || list->format == VGF_SOLANA || ctxs[0]->format == VGF_SOLANA)
         return ctxs[0]->fail(VGEN_E_UNSUPPORTED, "vgen_scan_list: pattern lists are not provided for the solana format");
+    if (cfg_full.format == VGF_ONION || list->format == VGF_ONION || ctxs[0]->format == VGF_ONION)
+        return ctxs[0]->fail(VGEN_E_UNSUPPORTED, "vgen_scan_list: pattern lists are not provided for the onion format");
     if (!list->list) return ctxs[0]->fail(VGEN_E_INVALID, "vgen_scan_list needs a pattern list (vgen_filter_compile_list)");
     if (cfg_full.format != list->format) return ctxs[0]->fail(VGEN_E_INVALID, "scan format differs from the pattern list's format");
     cfg_full.case_insensitive = list->case_insensitive ? 1 : 0;   // the list carries it
